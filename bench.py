@@ -13,6 +13,12 @@ exchanges ghosts over RCCL.
 Rank 0 prints ONE JSON line. Timed region: device sync + barrier, K V-cycles (hipGraph
 replay), device sync + barrier; max over ranks. Inputs are resident in HBM. libpamg is loaded
 before torch, and torch stays off the GPU (gloo rendezvous only): see _lib.runtime_providers.
+
+A plain run does what the headline needs and no more: setup, upload, --warmup cycles, ONE timed
+region of --steps cycles, the result line (value, ms_per_step, config, setup time).
+--dump-outputs DIR writes the iterate the timed call left behind. --full adds every other leg to
+the same line: 5 timed regions (value = the median), rocprofv3 PMC passes, time to solution
+(PCG), per-kernel timings, the roofline, the CPU baseline and the parity check against the oracle.
 """
 from __future__ import annotations
 
@@ -41,8 +47,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--samples", type=int, default=5,
-                    help="timed regions of exactly --steps V-cycles each; value = the median")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="timed regions of exactly --steps V-cycles each; value = the median "
+                         "(default: 1, so --steps is the number of timed cycles; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: 5 timed regions, PMC passes, PCG time to solution, "
+                         "per-kernel timings, roofline, CPU baseline, parity with the oracle")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed cycle left in x (own rows, the caller's numbering) as "
+                         "DIR/x.npy, float64; above DUMP_MAX_ENTRIES entries a fixed seeded sample of them")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--grid", type=int, default=512, help="grid points per side")
     ap.add_argument("--kind", default="poisson3d",
@@ -87,6 +100,8 @@ def main():
                     help="time-to-solution leg: PCG with the V-cycle preconditioner to this "
                          "relative residual from x = 0 (0: skip)")
     args = ap.parse_args()
+    if args.samples is None:
+        args.samples = 5 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -95,7 +110,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     # counters first: the profiled child runs start before this process makes any HIP call
     live_pmc = None
-    if args.pmc == "auto" and world == 1 and not args.matrix and args.permute is None and not args.rcm:
+    if (args.full and args.pmc == "auto" and world == 1 and not args.matrix and args.permute is None
+            and not args.rcm):
         live_pmc = pmc_live(args)
 
     # libpamg first: it then binds to /opt/rocm's HIP 7.2 / RCCL 2.27.7 rather than the copies
@@ -108,8 +124,10 @@ def main():
     from parallel_amg_amd.solver import OPS, AMGSolver
 
     _lib.lib()  # fail loudly if libpamg.so is missing
-    import torch
-    import torch.distributed as dist
+    torch = dist = None
+    if world > 1:  # one part has nothing to rendezvous: no torch import on its start-up path
+        import torch
+        import torch.distributed as dist
 
     _lib.call("pamg_set_option", b"value_dict", int(args.value_dict))
     for kv in args.set:
@@ -218,6 +236,83 @@ def main():
     vps = args.steps / dt
     log(f"timed samples ({args.steps} V-cycles each, max over ranks): "
         + ", ".join(f"{t * 1e3:.1f} ms" for t in times))
+
+    # ---- what the timed call computed: x as its last cycle left it (before any other leg runs) ----
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x.own_values(), rank, world)
+
+    # fine-level nonzeros of the whole problem (every rank holds only its own rows)
+    nnz_fine = (sum(be.allgather({rank: int(H.levels[0][rank].A.nnz)})) if world > 1
+                else int(sum(H.levels[0][p].A.nnz for p in H.levels[0])))
+    out = {
+        "metric": METRIC,
+        "value": round(vps, 4),
+        "unit": "V-cycles/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (SPEC.md §S2 grid operator, b = A x*, x0 = 0)",
+        "config": {
+            "workload": f"{workload}, SA-AMG V({nu1},{nu2}) weighted-Jacobi, "
+                        f"{world} part(s)",
+            "n": int(H.offsets(0)[-1]), "nnz_fine": int(nnz_fine), "levels": S.L, "max_coarse": args.max_coarse,
+            "parallelism": f"row-slab partition p{world}" + (
+                "" if world == 1 else " (RCCL ghost exchange)" if args.transport == "rccl"
+                else " (host debug transport)"),
+            "graph": S.graph_state(),
+            "graph_mismatch_ranks": graph_mismatch,
+            "transport": args.transport if world > 1 else None,
+            # levels >= this one are held whole on every rank (SPEC §S7 agglomeration)
+            "replicated_from_level": int(S.rep_level) if world > 1 else None,
+            "value_dict": bool(args.value_dict),
+            # levels uploaded with a locality permutation (AMGSolver reorder)
+            "reordered_levels": S.reordered,
+            "options": list(args.set),
+        },
+        "full": bool(args.full),
+        "samples_ms_per_step": [round(t / args.steps * 1e3, 4) for t in times],
+        "setup_s": round(t_setup, 1),
+        "setup_products": args.setup,
+    }
+    if args.full:  # every rank: the legs hold collectives
+        out.update(full_legs(args, world, rank, be, ctx, H, S, A0, x, b, nu1, nu2, live_pmc,
+                             device_sync, barrier, torch, dist))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+DUMP_MAX_ENTRIES = 1 << 22  # 32 MiB of float64 per run, split evenly over the ranks
+
+
+def dump_outputs(path, x, rank, world):
+    """DIR/x.npy (N > 1: DIR/x_p<rank>.npy, this rank's own rows): the iterate after the last
+    timed cycle, float64. More than DUMP_MAX_ENTRIES / N entries: a fixed stratified sample, one
+    entry out of each of that many equal strides, at a seeded offset inside its stride (the seed
+    is a constant, so the positions depend on nothing but the vector's length)."""
+    os.makedirs(path, exist_ok=True)
+    x = np.ascontiguousarray(x, np.float64)
+    cap = DUMP_MAX_ENTRIES // world
+    if x.size > cap:
+        stride = x.size // cap  # >= 1; the strides cover [0, cap * stride) <= x.size
+        idx = np.arange(cap, dtype=np.int64) * stride + np.random.default_rng(20240517).integers(0, stride, cap)
+        x = x[idx]
+    np.save(os.path.join(path, "x.npy" if world == 1 else f"x_p{rank}.npy"), x)
+    log(f"dumped {x.size} entries of x to {path}")
+
+
+def full_legs(args, world, rank, be, ctx, H, S, A0, x, b, nu1, nu2, live_pmc, device_sync, barrier,
+              torch, dist) -> dict:
+    """--full: the legs beside the headline, run after the timed regions on the same solver; returns
+    their keys of the result line (x is overwritten)."""
+    from parallel_amg_amd import _lib
+    from parallel_amg_amd.solver import OPS
 
     # ---- time to solution: PCG (V-cycle preconditioner) from x = 0 to --pcg-rtol ----------
     pcg = None
@@ -353,41 +448,9 @@ def main():
     if traffic_over_ceiling:
         phys_bytes = post_fbytes
 
-    # fine-level nonzeros of the whole problem (every rank holds only its own rows)
-    nnz_fine = (sum(be.allgather({rank: int(H.levels[0][rank].A.nnz)})) if world > 1
-                else int(sum(H.levels[0][p].A.nnz for p in H.levels[0])))
+    out = {}
     if rank == 0:
-        gl_rows = int(H.offsets(0)[-1])
         out = {
-            "metric": METRIC,
-            "value": round(vps, 4),
-            "unit": "V-cycles/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (SPEC.md §S2 grid operator, b = A x*, x0 = 0)",
-            "config": {
-                "workload": f"{workload}, SA-AMG V({nu1},{nu2}) weighted-Jacobi, "
-                            f"{world} part(s)",
-                "n": gl_rows, "nnz_fine": int(nnz_fine), "levels": S.L, "max_coarse": args.max_coarse,
-                "parallelism": f"row-slab partition p{world}" + (
-                    "" if world == 1 else " (RCCL ghost exchange)" if args.transport == "rccl"
-                    else " (host debug transport)"),
-                "graph": S.graph_state(),
-                "graph_mismatch_ranks": graph_mismatch,
-                "transport": args.transport if world > 1 else None,
-                # levels >= this one are held whole on every rank (SPEC §S7 agglomeration)
-                "replicated_from_level": int(S.rep_level) if world > 1 else None,
-                "value_dict": bool(args.value_dict),
-                # levels uploaded with a locality permutation (AMGSolver reorder)
-                "reordered_levels": S.reordered,
-                "options": list(args.set),
-            },
             # level-0 fused passes (Options::jr_fuse) beside the separate sweeps they replace
             "fused_level0": fused,
             # fine SpMV (one launch = y = A0 x), the metric's "fine-SpMV HBM GB/s": the bytes its layout
@@ -406,7 +469,6 @@ def main():
             # layout streams about half of that, so this "CSR-equivalent" rate may exceed the peak
             "fine_spmv_csr_equiv_GBps": round(spmv_gbps, 1),
             "fine_spmv_csr_equiv_frac": round(spmv_gbps / HBM_PEAK_GBPS, 4),
-            "samples_ms_per_step": [round(t / args.steps * 1e3, 4) for t in times],
             "roofline": {
                 "kernel": kname + (" (level-0 chain of the pipelined cycles, one launch per cycle: post-smoothing "
                                    "Jacobi -> next pre-smoothing Jacobi -> residual, temporally blocked (z-marching, "
@@ -462,13 +524,9 @@ def main():
             "levels": levels,
             "exchange": exch,
             "time_to_solution": pcg,
-            "setup_s": round(t_setup, 1),
-            "setup_products": args.setup,
             "final_residual": float(hist[0]),
         }
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 def exchange_times(ctx, S, be, nu1, nu2, reps=20) -> dict:

@@ -37,6 +37,19 @@ inline double diag_of(const pamg_hcsr& A, int64_t i, int64_t row0) {
 
 bool valid(const pamg_hcsr* M) { return M && (int64_t)M->rp.size() == M->nr + 1; }
 
+// Reserve n entries and touch every page of that storage, one slice per thread. The resize that
+// follows zero-fills on one thread; with the pages already mapped it runs at memset speed
+// instead of one page fault per 4 KiB (512^3: 11 GB of columns and values).
+template <class T>
+void reserve_touched(std::vector<T>& v, int64_t n) {
+    v.reserve((size_t)n);
+    char* p = reinterpret_cast<char*>(v.data());
+    const int64_t pages = (n * (int64_t)sizeof(T) + 4095) / 4096;
+    if (!p) return;
+#pragma omp parallel for schedule(static)
+    for (int64_t g = 0; g < pages; ++g) p[g * 4096] = 0;
+}
+
 // Row-parallel CSR assembly: `fill(i, cols, vals)` appends row i's entries; rows are
 // computed in static per-thread chunks and concatenated in row order (deterministic).
 template <class RowFn>
@@ -195,6 +208,8 @@ int pamg_gen_grid(int kind, int64_t nx, int64_t ny, int64_t nz, double eps, int6
             for (int u = 0; u < nt; ++u) part[u + 1] += part[u];
             for (int64_t i = lo; i < hi; ++i) M->rp[i + 1] += part[t];
         }
+        reserve_touched(M->col, M->rp[m]);
+        reserve_touched(M->val, M->rp[m]);
         M->col.resize(M->rp[m]);
         M->val.resize(M->rp[m]);
 #pragma omp parallel for schedule(static)

@@ -25,7 +25,7 @@ def _free_port():
 def test_bench_two_ranks_host_transport():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-           "--steps", "3", "--warmup", "1", "--grid", "48", "--transport", "host"]
+           "--steps", "3", "--warmup", "1", "--grid", "48", "--transport", "host", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="2")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

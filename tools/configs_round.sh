@@ -11,7 +11,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 run() {  # name, bench args...
     local name=$1; shift
-    timeout -k 10 240 python3 -u bench.py --cpu-baseline off --steps 50 "$@" > "$OUT/cfg_$name.json" 2> "$OUT/cfg_$name.log"
+    timeout -k 10 240 python3 -u bench.py --full --cpu-baseline off --steps 50 "$@" > "$OUT/cfg_$name.json" 2> "$OUT/cfg_$name.log"
     echo "$name: $(python3 -c "import json,sys; print(json.loads(open('$OUT/cfg_$name.json').read().strip().splitlines()[-1])['value'])")"
 }
 run p128 --grid 128

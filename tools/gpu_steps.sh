@@ -63,11 +63,11 @@ for step in "$@"; do
         timeout -k 10 600 $PYT tests/test_gpu_local_world.py -m gpu > "$OUT/world.log" 2>&1
         ;;
     bench)
-        timeout -k 10 700 python3 -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.log"
+        timeout -k 10 700 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log"
         ;;
     trace)
         timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv \
-            -- python3 -u bench.py --steps 5 --cpu-baseline off --pmc off > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.log"
+            -- python3 -u bench.py --full --steps 5 --cpu-baseline off --pmc off > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.log"
         ;;
     anatomy)
         timeout -s KILL 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum \
@@ -91,25 +91,25 @@ for step in "$@"; do
     gen)
         # the general-matrix path: the elastic3d stand-in for Flan_1565 in natural
         # and randomly renumbered order, and 512^3 without the row-class dictionary
-        timeout -k 10 400 python3 -u bench.py --kind elastic3d --grid 80 --pcg-rtol 0 > "$OUT/gen_e80.json" 2> "$OUT/gen_e80.log"
+        timeout -k 10 400 python3 -u bench.py --full --kind elastic3d --grid 80 --pcg-rtol 0 > "$OUT/gen_e80.json" 2> "$OUT/gen_e80.log"
         echo "gen e80 done"
-        timeout -k 10 400 python3 -u bench.py --kind elastic3d --grid 80 --permute 1 --pcg-rtol 0 > "$OUT/gen_e80p.json" 2> "$OUT/gen_e80p.log"
+        timeout -k 10 400 python3 -u bench.py --full --kind elastic3d --grid 80 --permute 1 --pcg-rtol 0 > "$OUT/gen_e80p.json" 2> "$OUT/gen_e80p.log"
         echo "gen e80p done"
-        timeout -k 10 600 python3 -u bench.py --set sym_vd=0 --cpu-baseline off --pcg-rtol 0 > "$OUT/gen_svd0.json" 2> "$OUT/gen_svd0.log"
+        timeout -k 10 600 python3 -u bench.py --full --set sym_vd=0 --cpu-baseline off --pcg-rtol 0 > "$OUT/gen_svd0.json" 2> "$OUT/gen_svd0.log"
         echo "gen svd0 done"
         ;;
     cfgs)
         # the other BASELINE configs at one GPU (bench lines with their oracle parity and CPU baseline)
-        timeout -k 10 300 python3 -u bench.py --grid 128 > "$OUT/cfg_p128.json" 2> "$OUT/cfg_p128.log"
+        timeout -k 10 300 python3 -u bench.py --full --grid 128 > "$OUT/cfg_p128.json" 2> "$OUT/cfg_p128.log"
         echo "cfg p128 done"
-        timeout -k 10 500 python3 -u bench.py --kind aniso3d --grid 256 > "$OUT/cfg_a256.json" 2> "$OUT/cfg_a256.log"
+        timeout -k 10 500 python3 -u bench.py --full --kind aniso3d --grid 256 > "$OUT/cfg_a256.json" 2> "$OUT/cfg_a256.log"
         echo "cfg a256 done"
         ;;
     gentrace)
         for spec in "e80:--kind elastic3d --grid 80" "e80p:--kind elastic3d --grid 80 --permute 1" "svd0:--set sym_vd=0"; do
             tag=${spec%%:*}
             timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$tag" -o bench --output-format csv \
-                -- python3 -u bench.py ${spec#*:} --steps 5 --samples 1 --cpu-baseline off --pmc off --pcg-rtol 0 \
+                -- python3 -u bench.py --full ${spec#*:} --steps 5 --samples 1 --cpu-baseline off --pmc off --pcg-rtol 0 \
                 > "$OUT/prof_$tag.json" 2> "$OUT/prof_$tag.log"
             echo "gentrace $tag done"
         done

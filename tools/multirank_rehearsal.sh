@@ -15,7 +15,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for N in $NS; do
     timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-        --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 5 --warmup 2 \
+        --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --full --gpus $N --steps 5 --warmup 2 \
         --samples 2 --grid $GRID --transport host > "$OUT/rehearsal_n${N}_g$GRID.json" 2> "$OUT/rehearsal_n${N}_g$GRID.log"
     echo "N=$N: $(tail -1 "$OUT/rehearsal_n${N}_g$GRID.json" | cut -c1-160)"
 done

@@ -11,10 +11,10 @@ export TMPDIR=/tmp
 TAG=${1:-r01}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-timeout -k 10 300 python3 -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.log"
+timeout -k 10 300 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log"
 echo "bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv \
-    -- python3 -u bench.py --steps 5 --cpu-baseline off > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.log"
+    -- python3 -u bench.py --full --steps 5 --cpu-baseline off --pmc off > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.log"
 echo "kernel trace done"
 KB="tools/kbench.py --n 512 --levels 1 --ops 0,2,5 --reps 3 --configs 1024"
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o fetch --output-format csv \
