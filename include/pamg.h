@@ -216,6 +216,14 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes);
  * (pnc_compact; out[4] = the combinations); bit 13: with bit 9, one index byte per nonzero names an
  * (offset, value) pair of the group (ell_pair). */
 int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
+/* The windowed sliced-ELL layout of a matrix (ell_xwin; with pamg_mat_layout bits 9 and 13): out[0]
+ * 1 where the matrix runs in it (else all 0), out[1] the groups whose x window is staged in LDS,
+ * out[2] the groups that gather, out[3] the largest window (doubles), out[4] the windowed groups
+ * whose slices are not consecutive, out[5] the largest pair table, out[6] the most load chunks of a
+ * group, out[7] the groups; the upload's census over the windowed groups: out[8] / out[9] the mean
+ * and 95th-percentile window, out[10] / out[11] the mean and largest number of column runs, out[12]
+ * the mean pair table, out[13] the groups of 4 slices; out[14], out[15] 0. */
+int pamg_mat_ell_window(const pamg_mat* A, int out[16]);
 
 /* mul!(y, A, x): exchanges x's ghosts (overlapped with the interior rows), then y = A x. */
 int pamg_spmv(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, pamg_vec* y);
@@ -311,7 +319,10 @@ int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps
  * prolongations over a grid uploaded earlier on the context), "rpat" (0 | 1: pattern-dictionary
  * rows for restrictions whose rows repeat <= 255 patterns; tried before ELL), "pnc_compact" (0 | 1:
  * neighbour-coded rows as 16-bit ids of <= 1024 (pattern, values) combinations), "ell_pair" (0 | 1:
- * one ELL index byte per nonzero naming an (offset, value) pair where a group has <= 256). Read at launch:
+ * one ELL index byte per nonzero naming an (offset, value) pair where a group has <= 256), "ell_xwin"
+ * (0 | 1: windowed ELL for whole square one-part operators with pair tables — groups of 4 coupled
+ * slices, their x neighbourhood staged in LDS), "ell_xwin_max" (2..7168: window capacity in doubles;
+ * a larger group gathers). Read at launch:
  * "sym_zm" (0 | 1: z-marching single sweeps of the symmetric layout), "zm_chunks" (0 = auto |
  * z chunks per column of k_sym_zm), "tb_xfast" (0 | 1: x-fastest tile order of the chain),
  * "symd_chunks" (1 | 2 | 4), "chain_store_x" (0 | 1). Applied at every exchange:

@@ -412,6 +412,13 @@ function layout(A::DeviceMatrix, set::Integer = 0)
      tm = out[6] != 0, tm_rs = Int(out[7]), tile_nnz = Int(out[8]), tiles = Int(out[9]), anchored = (out[10] & 1) != 0, per_tile = (out[10] & 2) != 0,
      x_stage = (out[10] & 4) != 0)
 end
+"The windowed sliced-ELL layout of a matrix (`ell_xwin`): whether it runs in it, its windowed and gathering groups, the largest window."
+function ell_window(A::DeviceMatrix)
+    out = zeros(Cint, 16)
+    check(ccall((:pamg_mat_ell_window, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cint}), A.h, out))
+    (ell_xwin = out[1] != 0, xwin_groups = Int(out[2]), gather_groups = Int(out[3]), max_window = Int(out[4]),
+     noncontig_groups = Int(out[5]), max_pairs = Int(out[6]), max_chunks = Int(out[7]), groups = Int(out[8]))
+end
 Base.size(A::DeviceMatrix) = (A.nrows, A.ncols_local)
 
 "mul!(y, A, x): ghost exchange of x (RCCL, overlapped with the interior rows), then y = A x."

@@ -81,6 +81,7 @@ SIGNATURES = {
     "pamg_mat_info": [vp, pi64, pi64, pi64],
     "pamg_mat_stream_bytes": [vp, pi64],
     "pamg_mat_layout": [vp, i32, C.POINTER(C.c_int)],
+    "pamg_mat_ell_window": [vp, C.POINTER(C.c_int)],
     "pamg_spmv": [vp, vp, vp, vp],
     "pamg_residual": [vp, vp, vp, vp, vp, pdbl],
     "pamg_jacobi": [vp, vp, vp, vp, vp, dbl, i32],
@@ -189,14 +190,23 @@ def layout_of(M, part_set: int = 0) -> dict:
     """The tile layout libpamg chose at upload for a device matrix (pamg_mat_layout)."""
     out = (C.c_int * 10)()
     call("pamg_mat_layout", M.handle, part_set, out)
-    return {"c24": bool(out[0]), "vd": bool(out[1]), "rl8": bool(out[2]), "cd": int(out[3]),
+    win = (C.c_int * 16)()
+    if part_set == 0:
+        call("pamg_mat_ell_window", M.handle, win)
+    return {"ell_xwin": bool(win[0]), "ell_xwin_groups": int(win[1]), "ell_gather_groups": int(win[2]),
+            "ell_xwin_max_window": int(win[3]), "ell_xwin_noncontig_groups": int(win[4]),
+            "ell_xwin_max_pairs": int(win[5]), "ell_xwin_max_chunks": int(win[6]),
+            "ell_xwin_census": {"groups": int(win[7]), "full_groups": int(win[13]), "window_mean": int(win[8]),
+                                "window_p95": int(win[9]), "runs_mean": int(win[10]), "runs_max": int(win[11]),
+                                "pairs_mean": int(win[12])},
+            "c24": bool(out[0]), "vd": bool(out[1]), "rl8": bool(out[2]), "cd": int(out[3]),
             "cd_offsets": int(out[4]), "tm": bool(out[5]), "tm_rs": int(out[6]),
             "tile_nnz": int(out[7]), "tiles": int(out[8]), "anchored": bool(out[9] & 1), "per_tile": bool(out[9] & 2),
             "x_stage": bool(out[9] & 4), "sym": bool(out[9] & 8), "sym_rows": 2 if out[9] & 16 else 1,
             "jr_fused": bool(out[9] & 32), "tm_vd": bool(out[9] & 64), "sym_vd": bool(out[9] & 128),
             "ell": bool(out[9] & 512), "pnc": bool(out[9] & 1024),
             "rpat": bool(out[9] & 2048), "pnc_compact": bool(out[9] & 4096),
-            "ell_pair": bool(out[9] & 8192)}
+            "ell_pair": bool(out[9] & 8192)}  # (ell_xwin*: pamg_mat_ell_window)
 
 
 def last_error() -> str:

@@ -1787,6 +1787,161 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ell(int nrows, const int* __
     if (in) y[i] = out;
 }
 
+// Four nonzeros of a lane's row for k_rows_ellw: the dword cq holds the pair bytes of entries
+// 4q .. 4q+3. WIN: the pair byte gives the value and the wave's lof word from LDS, x is read from
+// the staged window at lof + lane (consecutive lanes, consecutive slots); a padded entry reads slot
+// `lane`. Otherwise the pair's offset from LDS and x gathered at row + offset. The same products and
+// sums as k_rows_ell, in the same order.
+template <bool WIN>
+__device__ __forceinline__ void ellw_dword(uint32_t cq, int q, int L, int lane, int row,
+                                           const double* __restrict__ lv, const uint16_t* __restrict__ lof,
+                                           const double* __restrict__ lx, const int* __restrict__ lo,
+                                           const double* __restrict__ x, double& s) {
+    int of[4];
+    double vv[4], xv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const uint32_t p = (cq >> (8 * e)) & 255u;
+        vv[e] = lv[p];
+        if constexpr (WIN) of[e] = (int)lof[p] - 64 + lane;
+        else of[e] = lo[p];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if constexpr (WIN) xv[e] = lx[4 * q + e < L ? of[e] : lane];
+        else xv[e] = x[4 * q + e < L ? row + of[e] : row];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool ok = 4 * q + e < L;
+        const double p = vv[e] * xv[e];
+        const double t = s + p;
+        s = ok ? t : s;
+    }
+}
+
+// the index dwords q0 .. q0 + kEllwPre - 1 of a lane's row in one batch of loads (past the slice's
+// last dword: that dword again; a slice without dwords: the stream's first word)
+constexpr int kEllwPre = 12;
+__device__ __forceinline__ void ellw_load(uint32_t (&cq)[kEllwPre], const uint32_t* __restrict__ cw, int first, int nq,
+                                          int q0) {
+#pragma unroll
+    for (int e = 0; e < kEllwPre; ++e) cq[e] = cw[nq > 0 ? first + min(q0 + e, nq - 1) * kEllW : 0];
+}
+
+// k_rows_ellw: the windowed sliced ELL (pamg::EllSet::win; the 512^3 level-1 operator). As
+// k_rows_ell with pair tables, but a workgroup's 4 waves take the 4 coupled slices of its group
+// (gslices; -1: the wave only meets the barrier), and the x entries the group's rows read are loaded
+// once, before anything waits: every chunk (<= 64 x 16 bytes of consecutive columns) is one
+// direct-to-LDS load, the waves taking chunks w, w + 4, ..., and a lane's first kEllwPre index dwords
+// (48 nonzeros: the whole row at 512^3) are loaded beside them. Then one barrier, and a lane walks its
+// row with every operand in LDS or in registers. A group without a window (wmeta .y == 0: larger than the capacity),
+// or every group where x is not 16-byte aligned, takes the gathers of k_rows_ell (a workgroup-uniform
+// branch). Dynamic LDS: [win] doubles of window (>= 128: a gather group's offsets live there), 256
+// values, 4 x 256 lof words. Jacobi takes the diagonal from the row's diagonal position (dpos: the entry
+// with offset 0, as k_rows_ell finds it; 255: none), its index dword loaded beside the others: no
+// per-entry test in the walk. The window loads read up to one double past the last column (x vectors
+// carry 8 trailing doubles).
+template <int OP>
+__global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* __restrict__ gslices,
+                                                         const int2* __restrict__ smeta, const uint32_t* __restrict__ cw,
+                                                         const uint8_t* __restrict__ len, const uint8_t* __restrict__ dpos,
+                                                         const int4* __restrict__ gmeta, const int* __restrict__ otab,
+                                                         const double* __restrict__ vtab, const int4* __restrict__ wmeta, const int2* __restrict__ chunks,
+                                                         const uint16_t* __restrict__ lofs, int win, int gather_all,
+                                                         int ngroups, const double* __restrict__ x,
+                                                         const double* __restrict__ b, double* __restrict__ y,
+                                                         double omega) {
+    extern __shared__ double ellw_lds[];
+    double* lx = ellw_lds;
+    double* lv = ellw_lds + win;
+    uint16_t* lof = reinterpret_cast<uint16_t*>(lv + 256);
+    const int per = (ngroups + 7) / 8;
+    const int g = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if (g >= ngroups) return;  // the whole workgroup, before the barrier
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int4 gm = gmeta[g], wm = wmeta[g], gs = gslices[g];
+    // what depends on the group alone first: the tables, the lof words and the wave's chunk words (lane k:
+    // chunk w + 4k; <= kEllWinChunks / 4 = 64 a wave) are in flight with the slice's metadata
+    const int np = gm.y;
+    const bool windowed = wm.y > 0 && !gather_all;
+    const double vtv = vtab[gm.x + (tid < np ? tid : 0)];
+    const uint32_t* __restrict__ l32 = reinterpret_cast<const uint32_t*>(lofs + wm.z);  // (wm.z: a multiple of 4)
+    const uint32_t la = l32[windowed && tid < 2 * np ? tid : 0], lb = l32[windowed && tid + 256 < 2 * np ? tid + 256 : 0];
+    const int2 cmv = chunks[wm.x + (w + 4 * lane < wm.y ? w + 4 * lane : 0)];
+    const int slice = w == 0 ? gs.x : w == 1 ? gs.y : w == 2 ? gs.z : gs.w;
+    const int i = slice * kEllW + lane;
+    const bool in = slice >= 0 && i < nrows;
+    const int ic = in ? i : 0;
+    const int L = in ? (int)len[ic] : 0;
+    const int2 sm = smeta[slice >= 0 ? slice : 0];
+    const int nq = slice >= 0 ? (sm.y + 3) >> 2 : 0;
+    const uint32_t* __restrict__ cp = cw + sm.x + lane;
+    double pb = 0.0, px = 0.0, py = 0.0;
+    if constexpr (OP == OP_RESID || OP == OP_JACOBI) pb = b[ic];
+    if constexpr (OP == OP_JACOBI) px = x[ic];
+    if constexpr (OP == OP_PROLONG) py = y[ic];
+    uint32_t dkw = 0u;
+    int dk = 255;
+    if constexpr (OP == OP_JACOBI) {
+        dk = in ? (int)dpos[ic] : 255;
+        dkw = cw[dk != 255 ? sm.x + lane + (dk >> 2) * kEllW : 0];
+    }
+    double s = 0.0;
+    if (windowed) {
+        uint32_t cq[kEllwPre];
+        ellw_load(cq, cw, sm.x + lane, nq, 0);
+        for (int k = 0; w + 4 * k < wm.y; ++k) {
+            const int col = __builtin_amdgcn_readlane(cmv.x, k), sc = __builtin_amdgcn_readlane(cmv.y, k);
+            if (lane < (sc >> 16))
+                __builtin_amdgcn_global_load_lds(
+                    (const __attribute__((address_space(1))) void*)(x + col + 2 * lane),
+                    (__attribute__((address_space(3))) void*)(lx + (sc & 0xffff)), 16, 0, 0);
+        }
+        if (tid < np) lv[tid] = vtv;
+        if (tid < 2 * np) reinterpret_cast<uint32_t*>(lof)[tid] = la;
+        if (tid + 256 < 2 * np) reinterpret_cast<uint32_t*>(lof)[tid + 256] = lb;
+        __syncthreads();
+        for (int q0 = 0; q0 < nq; q0 += kEllwPre) {
+            if (q0 > 0) ellw_load(cq, cw, sm.x + lane, nq, q0);
+#pragma unroll
+            for (int e = 0; e < kEllwPre; ++e)
+                if (q0 + e < nq)  // (wave-uniform)
+                    ellw_dword<true>(cq[e], q0 + e, L, lane, ic, lv, lof + w * np, lx, nullptr, x, s);
+        }
+    } else {
+        int* lo = reinterpret_cast<int*>(lx);
+        const int otv = otab[gm.x + (tid < np ? tid : 0)];
+        if (tid < np) {
+            lo[tid] = otv;
+            lv[tid] = vtv;
+        }
+        __syncthreads();
+        uint32_t c4 = nq > 0 ? cp[0] : 0u;
+        for (int q = 0; q < nq; ++q) {
+            const uint32_t cq = c4;
+            if (q + 1 < nq) c4 = cp[(q + 1) * kEllW];  // the next dword in flight while this one is used
+            ellw_dword<false>(cq, q, L, lane, ic, lv, nullptr, nullptr, lo, x, s);
+        }
+    }
+    double out;
+    if constexpr (OP == OP_SPMV) {
+        out = s;
+    } else if constexpr (OP == OP_RESID) {
+        out = pb - s;
+    } else if constexpr (OP == OP_JACOBI) {
+        const double u = pb - s;
+        const double v = omega * u;
+        const double dg = dk != 255 ? lv[(dkw >> (8 * (dk & 3))) & 255u] : 0.0;
+        const double wq = v / dg;
+        out = px + wq;
+    } else {
+        out = py + s;
+    }
+    if (in) y[i] = out;
+}
+
 // k_rows_rpat: pattern-dictionary rows (pamg::RpatSet; round 6, the 512^3 R0). One row per lane, a
 // workgroup per kEllGroup rows (the groups in the ELL's blocked order where the columns are a
 // registered grid); every workgroup stages the entry, pattern and value tables (<= kRpatEnt + kRpatMax
@@ -2417,7 +2572,14 @@ void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const
             kern<<<grid, kEllGroup, 0, s>>>((int)A.nrows, E.d_gorder, E.d_anc, E.d_smeta, E.d_ci, E.d_vi, E.d_len,
                                             E.d_gmeta, E.d_otab, E.d_vtab, (int)E.ngroups, x, b, y, omega);
         };
-        if (E.d_anc) {
+        if (E.win) {
+            const int win = std::max(E.max_window, 128);
+            const size_t lds = sizeof(double) * (size_t)(win + 256) + sizeof(uint16_t) * 4 * 256;
+            k_rows_ellw<OP><<<grid, kEllGroup, lds, s>>>(
+                (int)A.nrows, E.d_gslices, E.d_smeta, E.d_ci, E.d_len, E.d_dpos, E.d_gmeta, E.d_otab, E.d_vtab, E.d_wmeta,
+                E.d_chunks, E.d_lof, win, (reinterpret_cast<uintptr_t>(x) & 15) != 0 ? 1 : 0, (int)E.ngroups, x, b, y,
+                omega);
+        } else if (E.d_anc) {
             if (E.paired) go(k_rows_ell<OP, true, true>);
             else go(k_rows_ell<OP, true, false>);
         } else {

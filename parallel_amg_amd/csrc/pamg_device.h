@@ -152,6 +152,11 @@ struct Options {
                                //    block of 2..64 lines, profiles/r05_r/); read at upload
     int rpat = 1;              // 1: pattern-dictionary rows for restrictions whose rows repeat few patterns (RpatSet)
     int ell_pair = 1;          // 1: one index byte per ELL nonzero naming an (offset, value) pair where they fit
+    int ell_xwin = 1;          // 1: windowed ELL for whole square one-part operators with pair tables (EllSet::win):
+                               //    groups of 4 coupled slices whose x neighbourhood is staged in LDS. Taken where
+                               //    >= kEllWinMinShare percent of the groups are windowed and their nonzeros per
+                               //    window entry are >= kEllWinMinRatio100 / 100 (below: the thresholds)
+    int ell_xwin_max = 7168;   // window capacity in doubles (<= kEllWinCap, the kernel's: 56 KB of its 60 KB of LDS)
     int pnc_compact = 1;       // 1: 16-bit combination ids instead of 64-bit records where <= kPncCombMax fit
     int pnc = 1;               // 1: neighbour-coded prolongations over a grid registered on the context (PncSet)
     int sym_vd = 1;            // 1: row-class dictionary for the symmetric layout where the rows take <= kSymVdMax
@@ -194,6 +199,22 @@ struct TbGeom {
 constexpr int kEllW = 64;
 constexpr int kEllGroup = 256;
 constexpr int kEllSkip = 255;  // length byte of a row outside the set (several parts: a boundary row)
+// Windowed ELL (Options::ell_xwin; k_rows_ellw): a workgroup's 4 slices are chosen by coupling, not
+// consecutive (d_gslices, -1: none), the x entries their rows read are runs of consecutive columns
+// loaded once into LDS in chunks of <= 64 x 16 bytes (d_chunks: first column — even —, LDS slot |
+// double2 count << 16), and the x of a nonzero of wave w naming pair p is lx[lof[w][p] + lane]
+// (d_lof: 16-bit words per group in [wave][pair] order: lof + 64); d_dpos is each row's diagonal
+// position (the entry with offset 0; 255: none), for Jacobi. A group whose window exceeds ell_xwin_max or kEllWinChunks chunks gathers as k_rows_ell
+// does (d_wmeta .y == 0). Acceptance: the operator takes the layout where at least kEllWinMinShare
+// percent of its groups are windowed and those groups hold at least kEllWinMinRatio100 / 100 nonzeros
+// per window entry (a 7-point grid's 4-line groups hold 2.0, the 512^3 A1 3.1; at 1.0 every entry
+// would be loaded for one use, the gathers' own traffic).
+constexpr int kEllWinCap = 7168;
+constexpr int kEllWinChunks = 256;  // (a wave reads its <= 64 chunk words with one load)
+constexpr int kEllLdsPerCu = 160 * 1024;
+constexpr int kEllWinKeep = 85;  // percent of the windowed groups kept when the largest window is lowered for occupancy
+constexpr int kEllWinMinShare = 50;
+constexpr int kEllWinMinRatio100 = 150;
 struct EllSet {
     int64_t nslices = 0, ngroups = 0;
     int2* d_smeta = nullptr;     // per slice: (first dword of its index streams, maxlen)
@@ -212,6 +233,18 @@ struct EllSet {
     // paired dictionaries (Options::ell_pair): one index byte per nonzero names an (offset, value)
     // pair of the group (d_otab / d_vtab entries in parallel, gmeta .x == .z, .y == .w); d_vi null
     bool paired = false;
+    // windowed (Options::ell_xwin; then paired, d_anc and d_gorder null, ngroups = the coupled groups)
+    bool win = false;
+    int4* d_gslices = nullptr;   // per group: its waves' slices (-1: none)
+    int4* d_wmeta = nullptr;     // per group: (first chunk, chunks — 0: gather —, first d_lof word, window doubles)
+    int2* d_chunks = nullptr;
+    uint16_t* d_lof = nullptr;
+    uint8_t* d_dpos = nullptr;
+    int64_t nchunks = 0, lof_n = 0;
+    int win_groups = 0, gather_groups = 0, noncontig_groups = 0;
+    int max_window = 0, max_pairs = 0, max_chunks = 0;  // over the windowed groups (max_pairs: all groups)
+    // census of the upload (pamg_mat_ell_window): windows, runs and pairs per windowed group, 4-slice groups
+    int mean_window = 0, p95_window = 0, mean_runs = 0, max_runs = 0, mean_pairs = 0, full_groups = 0;
 };
 
 // Neighbour-coded prolongation (Options::pnc; round 5, the 512^3 P0): a prolongation (more rows than

@@ -9,6 +9,7 @@
 #include <array>
 #include <atomic>
 #include <functional>
+#include <iterator>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -1312,6 +1313,340 @@ int blocked_group_order(pamg_ctx* ctx, const std::vector<int>& anc, int64_t ng, 
     return PAMG_OK;
 }
 
+// Windowed sliced ELL (Options::ell_xwin, pamg::EllSet::win; k_rows_ellw): the whole of a square
+// one-part operator. The slices and their index streams are build_ell's; a workgroup's 4 slices are
+// chosen by coupling instead of 4g .. 4g+3, so that their rows read a compact set of columns (the
+// 512^3 A1: 64 x 2 x 2 aggregates, 3.1 nonzeros per window entry against 1.9 for 256 consecutive
+// rows), and that set — runs of consecutive columns — is what the kernel loads into LDS in place of
+// the per-nonzero gathers. Greedy grouping: the lowest unassigned slice, then three times the
+// unassigned slice holding the most columns of the group's nonzeros (ties: the lower slice) among
+// the best six whose pairs keep the group's (offset, value) dictionary within 256; none of the six
+// fits: the group closes short. Declines (build_ell goes on with consecutive groups) where a slice
+// alone holds more than 256 pairs or the operator misses the acceptance thresholds (pamg_device.h).
+int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val,
+                   const std::vector<int2>& smeta, int64_t words) {
+    using pamg::kEllW;
+    const int64_t n = A->nrows, ns = (n + kEllW - 1) / kEllW;
+    const int cap = std::min(pamg::options().ell_xwin_max, pamg::kEllWinCap);
+    auto pair_key = [](int off, uint64_t u) {
+        uint64_t h = (u ^ (u >> 29)) * 0x9E3779B97F4A7C15ull + (uint64_t)(uint32_t)off * 0xC2B2AE3D27D4EB4Full;
+        return h ^ (h >> 32);
+    };
+    // per slice: its distinct pairs (64-bit keys, sorted) and the slices its columns fall in
+    std::vector<std::vector<uint64_t>> spair(ns);
+    std::vector<std::vector<std::pair<int, int>>> scoup(ns);
+    std::atomic<bool> ok{true};
+    par_for(ns, [&](int64_t a, int64_t b) {
+        std::vector<uint64_t> h;
+        std::vector<int> t;
+        for (int64_t q = a; q < b && ok; ++q) {
+            h.clear();
+            t.clear();
+            for (int64_t i = q * kEllW; i < std::min(n, (q + 1) * kEllW); ++i)
+                for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+                    uint64_t u;
+                    std::memcpy(&u, &val[k], 8);
+                    h.push_back(pair_key(ci[k] - (int)i, u));
+                    t.push_back(ci[k] / kEllW);
+                }
+            std::sort(h.begin(), h.end());
+            h.erase(std::unique(h.begin(), h.end()), h.end());
+            if (h.size() > 256) ok = false;
+            spair[q] = h;
+            std::sort(t.begin(), t.end());
+            for (size_t e = 0; e < t.size();) {
+                size_t f = e;
+                while (f < t.size() && t[f] == t[e]) ++f;
+                if (t[e] != q) scoup[q].push_back({t[e], (int)(f - e)});
+                e = f;
+            }
+        }
+    });
+    if (!ok) return PAMG_OK;
+    // the greedy pass (serial: a few candidates per slice)
+    std::vector<std::array<int, 4>> grp;
+    grp.reserve(ns / 4 + 1);
+    {
+        std::vector<char> done(ns, 0);
+        std::vector<int> score(ns, 0), touched, cand;
+        std::vector<uint64_t> un, tmp;
+        auto couple = [&](int q) {
+            for (const auto& c : scoup[q])
+                if (!done[c.first]) {
+                    if (score[c.first] == 0) touched.push_back(c.first);
+                    score[c.first] += c.second;
+                }
+        };
+        for (int64_t first = 0; first < ns; ++first) {
+            if (done[first]) continue;
+            std::array<int, 4> g = {(int)first, -1, -1, -1};
+            done[first] = 1;
+            un = spair[first];
+            touched.clear();
+            couple((int)first);
+            for (int m = 1; m < 4; ++m) {
+                cand.clear();
+                for (int t : touched)
+                    if (!done[t]) cand.push_back(t);
+                if (cand.empty()) {  // nothing coupled is left: the next slice in row order
+                    int64_t t = first + 1;
+                    while (t < ns && done[t]) ++t;
+                    if (t < ns) cand.push_back((int)t);
+                }
+                const size_t top = std::min<size_t>(6, cand.size());
+                std::partial_sort(cand.begin(), cand.begin() + top, cand.end(), [&](int p, int q) {
+                    return score[p] != score[q] ? score[p] > score[q] : p < q;
+                });
+                int take = -1;
+                for (size_t c = 0; c < top && take < 0; ++c) {
+                    tmp.clear();
+                    std::set_union(un.begin(), un.end(), spair[cand[c]].begin(), spair[cand[c]].end(),
+                                   std::back_inserter(tmp));
+                    if (tmp.size() <= 256) take = cand[c];
+                }
+                if (take < 0) break;
+                un.swap(tmp);
+                g[m] = take;
+                done[take] = 1;
+                couple(take);
+            }
+            for (int t : touched) score[t] = 0;
+            grp.push_back(g);
+        }
+    }
+    std::vector<std::vector<std::pair<int, int>>>().swap(scoup);
+    std::vector<std::vector<uint64_t>>().swap(spair);
+    const int64_t ng = (int64_t)grp.size();
+    // per group: the pair table and the index bytes (as build_ell), the window's runs, chunks and lof words
+    std::vector<std::vector<int>> goff(ng);
+    std::vector<std::vector<uint64_t>> gval(ng);
+    std::vector<std::vector<int2>> gchunk(ng);
+    std::vector<std::vector<uint16_t>> glof(ng);
+    std::vector<int> gwin(ng, 0), gruns(ng, 0);
+    std::vector<int64_t> gnnz(ng, 0);
+    std::vector<uint32_t> cw(words + 1, 0u);
+    std::vector<uint8_t> len(n + kVecPad, 0), dpos(n + kVecPad, (uint8_t)255);
+    par_for(ng, [&](int64_t a, int64_t b) {
+        constexpr int kSlots = 1024;
+        std::vector<int> pid(kSlots), pstamp(kSlots, -1), pkey_o(kSlots);
+        std::vector<uint64_t> pkey_v(kSlots);
+        std::vector<int> o, lmin(4 * 256), lmax(4 * 256);
+        std::vector<uint64_t> v;
+        std::vector<std::array<int, 2>> rng;
+        std::vector<std::array<int, 3>> runs;  // (first column, end, slot)
+        for (int64_t g = a; g < b && ok; ++g) {
+            const int stamp = (int)(g - a);
+            o.clear();
+            v.clear();
+            for (int w = 0; w < 4 && ok; ++w) {
+                const int64_t q = grp[g][w];
+                if (q < 0) continue;
+                for (int64_t i = q * kEllW; i < std::min(n, (q + 1) * kEllW) && ok; ++i) {
+                    len[i] = (uint8_t)(rp[i + 1] - rp[i]);
+                    gnnz[g] += rp[i + 1] - rp[i];
+                    const int lane = (int)(i % kEllW);
+                    for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+                        const int kk = (int)(k - rp[i]);
+                        const int off = ci[k] - (int)i;
+                        if (off == 0) dpos[i] = (uint8_t)kk;
+                        uint64_t u;
+                        std::memcpy(&u, &val[k], 8);
+                        uint32_t h = (uint32_t)((((uint64_t)(uint32_t)off * 0x9E3779B1u) ^ u ^ (u >> 29)) *
+                                                0x9E3779B97F4A7C15ull >> 54);
+                        while (pstamp[h] == stamp && (pkey_o[h] != off || pkey_v[h] != u)) h = (h + 1) & (kSlots - 1);
+                        if (pstamp[h] != stamp) {
+                            if (o.size() == 256) {  // (two pairs with one 64-bit key in the greedy's count)
+                                ok = false;
+                                break;
+                            }
+                            pstamp[h] = stamp;
+                            pkey_o[h] = off;
+                            pkey_v[h] = u;
+                            pid[h] = (int)o.size();
+                            for (int x = 0; x < 4; ++x) {
+                                lmin[x * 256 + pid[h]] = kEllW;
+                                lmax[x * 256 + pid[h]] = -1;
+                            }
+                            o.push_back(off);
+                            v.push_back(u);
+                        }
+                        const int p = pid[h];
+                        lmin[w * 256 + p] = std::min(lmin[w * 256 + p], lane);
+                        lmax[w * 256 + p] = std::max(lmax[w * 256 + p], lane);
+                        const int64_t wd = smeta[q].x + (int64_t)(kk / 4) * kEllW + lane;
+                        cw[wd] |= (uint32_t)p << (8 * (kk % 4));
+                    }
+                }
+            }
+            if (!ok) break;
+            goff[g] = o;
+            gval[g] = v;
+            const int np = (int)o.size();
+            // the column ranges the waves read per pair, merged into runs that start on 16 bytes
+            // (ranges up to a cache line apart share a run)
+            rng.clear();
+            for (int w = 0; w < 4; ++w)
+                for (int p = 0; p < np; ++p)
+                    if (grp[g][w] >= 0 && lmax[w * 256 + p] >= 0) {
+                        const int c0 = grp[g][w] * kEllW + o[p];
+                        rng.push_back({c0 + lmin[w * 256 + p], c0 + lmax[w * 256 + p]});
+                    }
+            std::sort(rng.begin(), rng.end());
+            runs.clear();
+            for (const auto& r : rng) {
+                const int s = r[0] & ~1, e = (r[1] + 2) & ~1;
+                if (!runs.empty() && s <= runs.back()[1] + 16) runs.back()[1] = std::max(runs.back()[1], e);
+                else runs.push_back({s, e, 0});
+            }
+            int slots = 0, nch = 0;
+            for (auto& r : runs) {
+                r[2] = slots;
+                slots += r[1] - r[0];
+                nch += (r[1] - r[0] + 127) / 128;
+            }
+            if (slots == 0 || slots > cap || nch > pamg::kEllWinChunks) continue;  // a gather group
+            // (every load stays inside x and its pad: real columns, rounded to pairs)
+            if (runs.front()[0] < 0 || runs.back()[1] > ((int)A->ncols + 1)) continue;
+            gwin[g] = slots;
+            gruns[g] = (int)runs.size();
+            for (const auto& r : runs)
+                for (int c = r[0]; c < r[1]; c += 128)
+                    gchunk[g].push_back(make_int2(c, (r[2] + c - r[0]) | (std::min(128, r[1] - c) / 2) << 16));
+            glof[g].assign((size_t)4 * np, (uint16_t)64);
+            for (int w = 0; w < 4; ++w)
+                for (int p = 0; p < np; ++p) {
+                    uint16_t word = 64;
+                    if (grp[g][w] >= 0 && lmax[w * 256 + p] >= 0) {
+                        const int c0 = grp[g][w] * kEllW + o[p], c = c0 + lmin[w * 256 + p];
+                        size_t r = 0;
+                        while (r + 1 < runs.size() && runs[r + 1][0] <= c) ++r;
+                        word = (uint16_t)(runs[r][2] + c0 - runs[r][0] + 64);
+                    }
+                    glof[g][(size_t)w * np + p] = word;
+                }
+        }
+    });
+    if (!ok) return PAMG_OK;
+    // Occupancy: a workgroup's LDS is the operator's largest window + 4 KB of tables, and the kernel
+    // lives on the waves in flight (512^3 A1, windows up to 3552: 4 workgroups per CU 0.42 ms, capped
+    // at 2816 — 6 per CU, 14 % of the groups gathering — 0.38 ms). So the largest window is lowered to
+    // what k workgroups per CU allow, for the largest k <= 8 that keeps kEllWinKeep percent of the
+    // windowed groups; the groups above it gather.
+    {
+        int64_t have = 0;
+        for (int64_t g = 0; g < ng; ++g) have += gwin[g] > 0;
+        for (int k = 8; k >= 2 && have > 0; --k) {
+            const int fit = ((pamg::kEllLdsPerCu / k - 2048) / 8 - 256) & ~1;
+            int64_t keep = 0;
+            for (int64_t g = 0; g < ng; ++g) keep += gwin[g] > 0 && gwin[g] <= fit;
+            if (keep * 100 < pamg::kEllWinKeep * have) continue;
+            for (int64_t g = 0; g < ng; ++g)
+                if (gwin[g] > fit) {
+                    gwin[g] = 0;
+                    gchunk[g].clear();
+                    glof[g].clear();
+                }
+            break;
+        }
+    }
+    pamg::EllSet& E = A->ell;
+    int64_t win_nnz = 0, win_slots = 0, win_runs = 0, win_pairs = 0;
+    for (int64_t g = 0; g < ng; ++g) {
+        E.max_pairs = std::max(E.max_pairs, (int)goff[g].size());
+        bool contig = true;
+        for (int w = 1; w < 4; ++w) contig = contig && (grp[g][w] < 0 || grp[g][w] == grp[g][0] + w);
+        if (gwin[g] > 0) {
+            ++E.win_groups;
+            win_nnz += gnnz[g];
+            win_slots += gwin[g];
+            E.max_window = std::max(E.max_window, gwin[g]);
+            E.max_chunks = std::max(E.max_chunks, (int)gchunk[g].size());
+            if (!contig) ++E.noncontig_groups;
+            win_runs += gruns[g];
+            win_pairs += (int64_t)goff[g].size();
+            E.max_runs = std::max(E.max_runs, gruns[g]);
+            if (grp[g][3] >= 0) ++E.full_groups;
+        } else {
+            ++E.gather_groups;
+        }
+    }
+    if ((int64_t)E.win_groups * 100 < pamg::kEllWinMinShare * ng || win_nnz * 100 < pamg::kEllWinMinRatio100 * win_slots) {
+        E = pamg::EllSet{};
+        return PAMG_OK;
+    }
+    {
+        std::vector<int> ws;
+        for (int64_t g = 0; g < ng; ++g)
+            if (gwin[g] > 0) ws.push_back(gwin[g]);
+        std::sort(ws.begin(), ws.end());
+        E.p95_window = ws[(ws.size() - 1) * 95 / 100];
+        E.mean_window = (int)(win_slots / E.win_groups);
+        E.mean_runs = (int)(win_runs / E.win_groups);
+        E.mean_pairs = (int)(win_pairs / E.win_groups);
+    }
+    std::vector<int4> gmeta(ng), wmeta(ng), gsl(ng);
+    int64_t on = 0, cn = 0, ln = 0;
+    for (int64_t g = 0; g < ng; ++g) {
+        const int np = (int)goff[g].size();
+        gmeta[g] = make_int4((int)on, np, (int)on, np);
+        wmeta[g] = make_int4((int)cn, (int)gchunk[g].size(), (int)ln, gwin[g]);
+        gsl[g] = make_int4(grp[g][0], grp[g][1], grp[g][2], grp[g][3]);
+        on += np;
+        cn += (int64_t)gchunk[g].size();
+        ln += (int64_t)glof[g].size();
+    }
+    if (ln >= INT32_MAX || cn >= INT32_MAX) {
+        E = pamg::EllSet{};
+        return PAMG_OK;
+    }
+    std::vector<int> otab(on + 1, 0);
+    std::vector<double> vtab(on + 1, 0.0);
+    std::vector<int2> chunks(cn + 1, make_int2(0, 0));
+    std::vector<uint16_t> lof(ln + 2, (uint16_t)0);
+    par_for(ng, [&](int64_t a, int64_t b) {
+        for (int64_t g = a; g < b; ++g) {
+            std::copy(goff[g].begin(), goff[g].end(), otab.begin() + gmeta[g].x);
+            for (size_t e = 0; e < gval[g].size(); ++e) std::memcpy(&vtab[gmeta[g].x + e], &gval[g][e], 8);
+            std::copy(gchunk[g].begin(), gchunk[g].end(), chunks.begin() + wmeta[g].x);
+            std::copy(glof[g].begin(), glof[g].end(), lof.begin() + wmeta[g].z);
+        }
+    });
+    pamg_ctx* ctx = A->ctx;
+    E.nslices = ns;
+    E.ngroups = ng;
+    E.words = words;
+    E.otab_n = on;
+    E.vtab_n = on;
+    E.paired = true;
+    E.win = true;
+    E.nchunks = cn;
+    E.lof_n = ln;
+    CHECK(dalloc(&E.d_smeta, ns));
+    CHECK(dalloc(&E.d_ci, words + 1));
+    CHECK(dalloc(&E.d_len, n + kVecPad));
+    CHECK(dalloc(&E.d_gmeta, ng));
+    CHECK(dalloc(&E.d_otab, on + 1));
+    CHECK(dalloc(&E.d_vtab, on + 1));
+    CHECK(dalloc(&E.d_gslices, ng));
+    CHECK(dalloc(&E.d_wmeta, ng));
+    CHECK(dalloc(&E.d_chunks, cn + 1));
+    CHECK(dalloc(&E.d_lof, ln + 2));
+    CHECK(dalloc(&E.d_dpos, n + kVecPad));
+    CHECK(h2d(ctx, E.d_dpos, dpos.data(), dpos.size()));
+    CHECK(h2d(ctx, E.d_smeta, smeta.data(), sizeof(int2) * ns));
+    CHECK(h2d(ctx, E.d_ci, cw.data(), sizeof(uint32_t) * (words + 1)));
+    CHECK(h2d(ctx, E.d_len, len.data(), len.size()));
+    CHECK(h2d(ctx, E.d_gmeta, gmeta.data(), sizeof(int4) * ng));
+    CHECK(h2d(ctx, E.d_otab, otab.data(), sizeof(int) * (on + 1)));
+    CHECK(h2d(ctx, E.d_vtab, vtab.data(), sizeof(double) * (on + 1)));
+    CHECK(h2d(ctx, E.d_gslices, gsl.data(), sizeof(int4) * ng));
+    CHECK(h2d(ctx, E.d_wmeta, wmeta.data(), sizeof(int4) * ng));
+    CHECK(h2d(ctx, E.d_chunks, chunks.data(), sizeof(int2) * (cn + 1)));
+    CHECK(h2d(ctx, E.d_lof, lof.data(), sizeof(uint16_t) * (ln + 2)));
+    A->interior.ell = true;
+    return PAMG_OK;
+}
+
 // Sliced ELL with per-group dictionaries (Options::ell, pamg::EllSet): a square operator whose
 // rows are all interior, in slices of kEllW rows padded to the slice's longest row, kEllGroup
 // rows sharing one table of column offsets (col - row) and one of values (bit patterns), each of
@@ -1355,6 +1690,11 @@ int build_ell(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
         smeta[q] = make_int2((int)words, slen[q]);
         words += (int64_t)kEllW * ((slen[q] + 3) / 4);
         if (words >= INT32_MAX) return PAMG_OK;
+    }
+    // the whole of a square one-part operator: coupled groups with their x windows in LDS, where that pays
+    if (!anchored && in_set.empty() && !A->plan && pamg::options().ell_pair && pamg::options().ell_xwin) {
+        CHECK(build_ell_xwin(A, rp, ci, val, smeta, words));
+        if (A->interior.ell) return PAMG_OK;
     }
     // per group, one pass: an entry's offset and value take the index of their first appearance in
     // the group (open addressing over 512 slots, stamped per group instead of cleared), and the index
@@ -1910,6 +2250,11 @@ void free_ell(pamg::EllSet& E) {
     dfree(E.d_otab);
     dfree(E.d_vtab);
     dfree(E.d_anc);
+    dfree(E.d_gslices);
+    dfree(E.d_wmeta);
+    dfree(E.d_chunks);
+    dfree(E.d_lof);
+    dfree(E.d_dpos);
     E = pamg::EllSet{};
 }
 
@@ -3350,7 +3695,8 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
     // descriptors and the group tables
     if (A->interior.ell)
         A->stream_bytes += (A->ell.paired ? 4 : 8) * A->ell.words + nrows + 8 * A->ell.nslices + 16 * A->ell.ngroups + 4 * A->ell.otab_n +
-                           8 * A->ell.vtab_n + (A->ell.d_anc ? 4 * nrows : 0);
+                           8 * A->ell.vtab_n + (A->ell.d_anc ? 4 * nrows : 0) +
+                           (A->ell.win ? 32 * A->ell.ngroups + 8 * A->ell.nchunks + 2 * A->ell.lof_n + nrows : 0);
     // neighbour-coded prolongation: the anchor and the record per row, the two tables
     if (A->interior.pnc)
         A->stream_bytes += (A->pnc.d_cid ? 6 : 12) * nrows + (A->pnc.d_cid ? 12 : 4) * A->pnc.npat + 8 * A->pnc.nval;
@@ -3529,6 +3875,28 @@ int pamg_mat_layout(const pamg_mat* A, int set, int out[10]) {
         out[4] = A->sym.nu;
         out[8] = A->sym.nbands * 8 * A->sym.eighth;
     }
+    return PAMG_OK;
+}
+
+int pamg_mat_ell_window(const pamg_mat* A, int out[16]) {
+    if (!A || !out) return fail(PAMG_E_ARG, "mat_ell_window: bad args");
+    const pamg::EllSet& E = A->ell;
+    const bool w = A->interior.ell && E.win;
+    out[0] = w ? 1 : 0;
+    out[1] = w ? E.win_groups : 0;
+    out[2] = w ? E.gather_groups : 0;
+    out[3] = w ? E.max_window : 0;
+    out[4] = w ? E.noncontig_groups : 0;
+    out[5] = w ? E.max_pairs : 0;
+    out[6] = w ? E.max_chunks : 0;
+    out[7] = w ? (int)E.ngroups : 0;
+    out[8] = w ? E.mean_window : 0;
+    out[9] = w ? E.p95_window : 0;
+    out[10] = w ? E.mean_runs : 0;
+    out[11] = w ? E.max_runs : 0;
+    out[12] = w ? E.mean_pairs : 0;
+    out[13] = w ? E.full_groups : 0;
+    out[14] = out[15] = 0;
     return PAMG_OK;
 }
 
@@ -4198,6 +4566,8 @@ int pamg_set_option(const char* key, int64_t value) {
     else if (k == "rpat" && (value == 0 || value == 1)) o.rpat = (int)value;
     else if (k == "pnc_compact" && (value == 0 || value == 1)) o.pnc_compact = (int)value;
     else if (k == "ell_pair" && (value == 0 || value == 1)) o.ell_pair = (int)value;
+    else if (k == "ell_xwin" && (value == 0 || value == 1)) o.ell_xwin = (int)value;
+    else if (k == "ell_xwin_max" && value >= 2 && value <= pamg::kEllWinCap) o.ell_xwin_max = (int)value;
     else if (k == "ell_yblock" && value >= 0 && value <= 65536) o.ell_yblock = (int)value;
     else if (k == "ell_min_rows" && value >= 0 && value <= INT32_MAX) o.ell_min_rows = (int)value;
     else if (k == "zm_chunks" && value >= 0 && value <= 4096) o.zm_chunks = (int)value;
@@ -4239,6 +4609,8 @@ int pamg_get_option(const char* key, int64_t* value) {
     else if (k == "rpat") *value = o.rpat;
     else if (k == "pnc_compact") *value = o.pnc_compact;
     else if (k == "ell_pair") *value = o.ell_pair;
+    else if (k == "ell_xwin") *value = o.ell_xwin;
+    else if (k == "ell_xwin_max") *value = o.ell_xwin_max;
     else if (k == "ell_yblock") *value = o.ell_yblock;
     else if (k == "ell_min_rows") *value = o.ell_min_rows;
     else if (k == "zm_chunks") *value = o.zm_chunks;
