@@ -1233,6 +1233,89 @@ def test_rpat_declines(ctx):
         assert np.array_equal(bits(y.own_values()), bits(O.spmv(Mx, xh)))
 
 
+def _rpat_rows(pats, nrows=6000):
+    """A restriction-shaped matrix (nrows x 4 nrows + 192) whose row j copies pattern j % len(pats)
+    — (offsets from the row's first column 4 j, values), all distinct — so every pattern is in use and
+    pattern p has the id p."""
+    assert len({(tuple(o.tolist()), tuple(v.tolist())) for o, v in pats}) == len(pats)
+    L = np.array([len(o) for o, _v in pats], np.int64)
+    start = np.concatenate([[0], np.cumsum(L)])
+    po = np.concatenate([np.asarray(o, np.int64) for o, _v in pats])
+    pv = np.concatenate([np.asarray(v, np.float64) for _o, v in pats])
+    pid = np.arange(nrows) % len(pats)
+    rowptr = np.concatenate([[0], np.cumsum(L[pid])]).astype(np.int64)
+    row = np.repeat(np.arange(nrows), L[pid])
+    e = start[pid[row]] + np.arange(rowptr[-1]) - rowptr[row]
+    return O.CSR(rowptr, 4 * row + po[e], pv[e], 4 * nrows + 192)
+
+
+def _rpat_limit_case(name):
+    """(patterns, whether build_rpat takes them) at the limits of pamg_device.h: at most kRpatMax = 255
+    patterns, kRpatEnt = 4096 entries in all, 256 values, rows of 1 .. kRpatMaxLen = 128 entries."""
+    rng = np.random.default_rng(77)
+    pal = rng.standard_normal(12)
+
+    def short(j):  # 1 + j % 31 entries; patterns of one length differ in their first value (j < 372)
+        e = np.arange(1 + j % 31)
+        return e * (1 + j % 3), pal[(j + 5 * e) % 12]
+
+    def long_(j, m=128):  # offsets 0 .. m - 1; entries 0 and 1 tell the patterns apart (j < 36)
+        v = 5 * np.arange(m) % 12
+        v[0], v[1] = j % 12, j // 12
+        return np.arange(m), pal[v]
+
+    one = (np.array([0]), pal[:1])
+    if name in ("npat255", "npat256"):
+        pats = [short(j) for j in range(int(name[4:]))]
+        assert name != "npat255" or sum(len(o) for o, _v in pats) == 3996
+        return pats, name == "npat255"
+    if name in ("len128", "len129"):
+        return [short(j) for j in range(5)] + [long_(0), long_(1, int(name[3:])), long_(2)], name == "len128"
+    if name in ("ent4096", "ent4097"):
+        pats = [long_(j) for j in range(32)] + [one] * (name == "ent4097")
+        assert sum(len(o) for o, _v in pats) == int(name[3:])
+        return pats, name == "ent4096"
+    if name in ("val256", "val257"):
+        vals = rng.standard_normal(257)
+        assert len(np.unique(vals)) == 257
+        pats = [(3 * np.arange(16), vals[16 * j:16 * j + 16]) for j in range(16)]
+        return pats + [(np.array([0]), vals[256:])] * (name == "val257"), name == "val256"
+    assert name == "empty_row"
+    return [short(j) for j in range(1, 8)] + [(np.zeros(0, np.int64), np.zeros(0))], False
+
+
+@pytest.mark.parametrize("name", ["npat255", "npat256", "len128", "len129", "ent4096", "ent4097", "val256",
+                                  "val257", "empty_row"])
+def test_rpat_limits(ctx, name):
+    """build_rpat's limits from both sides (the last pattern id 254 next to kRpatSkip = 255, the full
+    pattern table, 4096 / 4097 entries, 256 / 257 values, rows of 128 / 129 entries, an empty row):
+    y = R r, b - R r and y += R r bit-exact with the oracle in the layout taken and in the tiles."""
+    import ctypes
+    from parallel_amg_amd._lib import call, layout_of
+    pats, takes = _rpat_limit_case(name)
+    M = _rpat_rows(pats)
+    A, _h = upload(ctx, M)
+    with _with_option("rpat", 0), _with_option("ell_restrict", 0):
+        B, _h2 = upload(ctx, M)
+    la, lb = layout_of(A), layout_of(B)
+    assert la["rpat"] == takes and not lb["rpat"] and not lb["ell"], (la, lb)
+    if takes:
+        assert la["cd_offsets"] == len(pats), la
+    rng = np.random.default_rng(5)
+    xh, bh = rng.standard_normal(M.ncols), rng.standard_normal(M.nrows)
+    s = O.spmv(M, xh)
+    for D in (A, B):
+        x, b, y = PVector(ctx, M.ncols, 0, xh), PVector(ctx, M.nrows, 0, bh), PVector(ctx, M.nrows)
+        mul(y, D, x)
+        assert np.array_equal(bits(y.own_values()), bits(s))
+        residual(y, D, x, b)
+        assert np.array_equal(bits(y.own_values()), bits(O.residual(M, xh, bh)))
+        ms, yy = ctypes.c_double(), PVector(ctx, M.nrows, 0, bh)
+        call("pamg_bench_rowop", ctx.handle, D.handle, 3, x.handle, None, yy.handle, 0.0, 1, ctypes.byref(ms))
+        # two launches (warm-up + 1 timed): bh + s + s, in that order
+        assert np.array_equal(bits(yy.own_values()), bits((bh + s) + s))
+
+
 def test_ell_level1_operator_128(ctx):
     """The level-1 operator of the 128^3 hierarchy (263,552 rows, 30 nonzeros per row: what the
     512^3 cycle runs per V-cycle twice) in the sliced-ELL layout: residual and Jacobi bit-exact with
