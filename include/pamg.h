@@ -240,6 +240,18 @@ int pamg_jacobi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b
  * same either way. fused may be NULL. */
 int pamg_jacobi_residual(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b,
                          pamg_vec* t, pamg_vec* r, double omega, int* fused);
+/* Chebyshev polynomial smoother (SPEC §S9) over the interval [lmax / ratio, lmax] of D^-1 A.
+ * pamg_chebyshev_coeffs (host only): the coefficients c1[k], c2[k], k = 0 .. degree-1, of the
+ * three-term steps, in fp64 in the order SPEC §S9 fixes (c1[0] = 0). PAMG_E_ARG unless
+ * lmax > 0, ratio > 1 and 1 <= degree <= 64. */
+int pamg_chebyshev_coeffs(double lmax, double ratio, int degree, double* c1, double* c2);
+/* One polynomial of the given degree on x (result in x): step 0 is a weighted-Jacobi sweep with
+ * omega = c2[0], step k >= 1 is x_{k+1} = x_k + (c1[k] (x_k - x_{k-1}) + (c2[k] (b - A x_k)) / a_ii).
+ * tmp1 and tmp2 are work vectors shaped like x (ghost slots included: both are read as A's
+ * input); x, tmp1, tmp2 and b must all differ. A is a square operator (PAMG_E_ARG for a
+ * prolongation or restriction). */
+int pamg_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp1,
+                   pamg_vec* tmp2, double lmax, double ratio, int degree);
 
 /* ------------------------------------------------------------------ hierarchy / V-cycle */
 /* Levels 0..nlevels-1; P[l], R[l] for l < nlevels-1 (NULL entries otherwise). The coarsest
@@ -263,6 +275,15 @@ int pamg_hier_set_graph(pamg_hier* H, int enable);
 /* V(nu1, nu2): Jacobi sweeps before / after the coarse correction (SPEC §S6; default 1, 1;
  * 1..64). The first pre-sweep on levels >= 1 is the zero-guess form. */
 int pamg_hier_set_sweeps(pamg_hier* H, int nu1, int nu2);
+/* The smoother of the V-cycle: PAMG_SMOOTHER_JACOBI (default; lmax and ratio ignored, lmax may be
+ * NULL) or PAMG_SMOOTHER_CHEBYSHEV — one polynomial of degree nu1 before and one of degree nu2
+ * after the coarse correction (the degrees are pamg_hier_set_sweeps'), level l over
+ * [lmax[l] / ratio, lmax[l]], lmax holding nlevels - 1 entries (SPEC §S9; lmax[l] > 0, ratio > 1,
+ * else PAMG_E_ARG). A Chebyshev hierarchy takes neither the temporally blocked passes nor the
+ * cross-cycle pipeline. Changing the smoother drops the captured graphs. */
+#define PAMG_SMOOTHER_JACOBI 0
+#define PAMG_SMOOTHER_CHEBYSHEV 1
+int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ratio);
 /* Level-0 numbering of a hierarchy whose operators were uploaded with pamg_mat_upload_perm
  * (one part only): device row i of level 0 is caller row perm[i]. pamg_vcycle(_async) and
  * pamg_pcg then take x and b in the caller's numbering — gathered into the device numbering at
@@ -292,15 +313,18 @@ int pamg_hier_profile_read(pamg_hier* H, double* ms_per_level_op /* nlevels*6 */
  * 1 residual, 2 Jacobi, 3 prolongate-add; no exchange; 4 / 5: the temporally blocked
  * Jacobi -> residual and Jacobi -> Jacobi -> residual passes, first output in y, where
  * pamg_mat_layout out[9] bit 5 is set), returning the average time per launch in ms measured
- * with HIP events on the launch stream. */
+ * with HIP events on the launch stream. Op 6 is one Chebyshev step k >= 1 (SPEC §S9) of a square
+ * operator: x is x_k, b the right-hand side, y the result, `omega` serves as both c1 and c2, and
+ * x_{k-1} is a zeroed vector the call allocates beside b for its duration (the argument list has
+ * no slot for it; the kernels stream it like any other). */
 int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, const pamg_vec* b,
                      pamg_vec* y, double omega, int reps, double* avg_ms);
 
 /* Micro-benchmark hook of the cross-cycle pipeline: `reps` launches of its level-0 chain kernel
  * (post-smoothing -> next pre-smoothing -> residual, k_sym_zc<3>) on the hierarchy's own level-0
  * buffers and the given x / b (x is overwritten); average ms per launch (HIP events).
- * PAMG_E_STATE when the hierarchy does not qualify (one part, V(1,1), jr_fuse, level 0 with
- * pamg_mat_layout bit 5). */
+ * PAMG_E_STATE when the hierarchy does not qualify (one part, V(1,1), the Jacobi smoother,
+ * jr_fuse, level 0 with pamg_mat_layout bit 5). */
 int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps, double* avg_ms);
 
 /* Process-wide knobs. Applied to later pamg_mat_upload calls: "tile_nnz" (1024 | 2048 | 4096,

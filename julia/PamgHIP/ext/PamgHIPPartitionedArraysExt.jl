@@ -368,16 +368,20 @@ end
 
 """
     HIPPVCycle(ctxs, A::PSparseMatrix; theta = 0.02, max_coarse = 1000, max_levels = 20,
-               agglomerate = 32768, gpu_products = true, ncycles = 1)
+               agglomerate = 32768, gpu_products = true, ncycles = 1, smoother = :jacobi,
+               cheb_ratio = 4.0, sweeps = (1, 1))
 
 Smoothed-aggregation hierarchy of A set up part by part (SPEC §S4; the driver of
 parallel_amg_amd/hierarchy.py), levels ≥ 1 with ≤ `agglomerate` rows gathered whole on every
-part (SPEC §S7), uploaded into one device VCycle per part. `ldiv!(x, M, b)` is one V-cycle.
+part (SPEC §S7), uploaded into one device VCycle per part. `ldiv!(x, M, b)` is one V-cycle,
+V(`sweeps`...) with the `smoother` chosen here: `:jacobi`, or `:chebyshev` over
+[rho_l / cheb_ratio, rho_l] with the setup's bounds rho_l (SPEC §S9; the sweeps are its degrees).
 A's rows must be a contiguous-block partition (uniform_partition / variable_partition).
 """
 function HIPPVCycle(ctxs, A::PSparseMatrix; theta::Real = 0.02, max_coarse::Integer = 1000,
                     max_levels::Integer = 20, agglomerate::Integer = 32768, gpu_products::Bool = true,
-                    ncycles::Integer = 1)
+                    ncycles::Integer = 1, smoother::Symbol = :jacobi, cheb_ratio::Real = 4.0,
+                    sweeps::Tuple{Integer,Integer} = (1, 1))
     rows = partition(axes(A, 1))
     nparts = length(rows)
     # replicated scalars / offsets are read with getany (the local part's copy under with_mpi)
@@ -407,7 +411,7 @@ function HIPPVCycle(ctxs, A::PSparseMatrix; theta::Real = 0.02, max_coarse::Inte
         omega = map(r -> 4.0 / (3.0 * r), rho)
         ghosts = map((M, p) -> nparts > 1 ? _ghost_ids(M, offs[p], offs[p+1]) : Int64[], Ah, parts)
         planA = _build_plans(ghosts, offs)
-        lev = Dict{Symbol,Any}(:A => Ah, :offs => offs, :omega => omega, :planA => planA)
+        lev = Dict{Symbol,Any}(:A => Ah, :offs => offs, :omega => omega, :rho => rho, :planA => planA)
         push!(levels, lev)
         (n <= max_coarse || length(levels) >= max_levels) && break
         aggs = map((M, p) -> PamgHIP.aggregate(M, offs[p], theta), Ah, parts)
@@ -458,6 +462,7 @@ function HIPPVCycle(ctxs, A::PSparseMatrix; theta::Real = 0.02, max_coarse::Inte
               (tail !== nothing && l == L) ? none : levels[l][:planP]) for l in withP]
     dR = [map((c, M, pl) -> _upload(c, M, pl, _plan_tag(l, :R)), ctxs, levels[l][:R], levels[l][:planR]) for l in withP]
     om = [lev[:omega] for lev in levels]
+    rh = [lev[:rho] for lev in levels]
     if tail === nothing
         # coarsest level: every part assembles the whole matrix and the same inverse
         full = nparts == 1 ? levels[end][:A] : _gather_full(levels[end][:A], levels[end][:offs])
@@ -468,16 +473,20 @@ function HIPPVCycle(ctxs, A::PSparseMatrix; theta::Real = 0.02, max_coarse::Inte
         rep, roffs = L, levels[end][:coffs]
     end
     nP = length(withP)
-    hier = map(ctxs, tail === nothing ? none : tail, ainv, dA..., dP..., dR..., om...) do ctx, Tv, ai, rest...
+    hier = map(ctxs, tail === nothing ? none : tail, ainv, dA..., dP..., dR..., om..., rh...) do ctx, Tv, ai, rest...
         a = DeviceMatrix[rest[1:L]...]
         pm = DeviceMatrix[rest[L+1:L+nP]...]
         rm = DeviceMatrix[rest[L+nP+1:L+2nP]...]
-        o = Float64[rest[L+2nP+1:end]...]
+        o = Float64[rest[L+2nP+1:2L+2nP]...]
+        rb = Float64[rest[2L+2nP+1:end]...]
         if Tv !== nothing
-            append!(a, Tv.A); append!(pm, Tv.P); append!(rm, Tv.R); append!(o, Tv.omega)
+            append!(a, Tv.A); append!(pm, Tv.P); append!(rm, Tv.R); append!(o, Tv.omega); append!(rb, Tv.rho)
         end
-        PamgHIP.VCycle(ctx, a, pm, rm, o, ai; rep_level = rep,
-                       rep_offsets = nparts > 1 ? Vector{Int64}(roffs) : nothing, ncycles = ncycles)
+        M = PamgHIP.VCycle(ctx, a, pm, rm, o, ai; rep_level = rep,
+                           rep_offsets = nparts > 1 ? Vector{Int64}(roffs) : nothing, ncycles = ncycles, rho = rb)
+        PamgHIP.set_sweeps!(M, sweeps[1], sweeps[2])
+        smoother === :jacobi || PamgHIP.set_smoother!(M, smoother; ratio = cheb_ratio)
+        M
     end
     HIPPVCycle(hier)
 end

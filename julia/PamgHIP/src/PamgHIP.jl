@@ -23,7 +23,7 @@ using SparseArrays
 # by the package extension with methods of PartitionedArrays' own generic functions, so a solver
 # that does `using PartitionedArrays, PamgHIP` calls them unqualified and unambiguously.
 export Context, ExchangePlan, DeviceVector, DeviceMatrix, HostCSR, VCycle, ExchangeTask, PamgError,
-       download_own, download_ghosts, exchange_begin, residual!, jacobi!, jacobi_residual!, vcycle!, pcg!, set_sweeps!,
+       download_own, download_ghosts, exchange_begin, residual!, jacobi!, jacobi_residual!, chebyshev!, chebyshev_coeffs, vcycle!, pcg!, set_sweeps!, set_smoother!,
        set_perm!, setup_hierarchy, gen_grid, gen_xstar, read_mtx, rcm_order, locality_order, unique_id,
        comm_init!, runtime_versions, hip, World, world_spmv!, world_exchange!, world_dot, world_vcycle!,
        world_pcg!, world_abort!, world_reset!, world_broken, set_tag!
@@ -438,6 +438,19 @@ jacobi!(x::DeviceVector, A::DeviceMatrix, b::DeviceVector, tmp::DeviceVector, om
     (check(ccall((:pamg_jacobi, libpamg), Cint,
                  (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint),
                  A.ctx.h, A.h, x.h, b.h, tmp.h, omega, nsweeps)); x)
+"The step coefficients (c1, c2) of the degree-`degree` Chebyshev smoother over [lmax / ratio, lmax] (SPEC §S9)."
+function chebyshev_coeffs(lmax::Real, ratio::Real = 4.0, degree::Integer = 2)
+    c1, c2 = zeros(max(degree, 1)), zeros(max(degree, 1))
+    check(ccall((:pamg_chebyshev_coeffs, libpamg), Cint, (Cdouble, Cdouble, Cint, Ptr{Float64}, Ptr{Float64}),
+                lmax, ratio, degree, c1, c2))
+    (c1, c2)
+end
+"One Chebyshev polynomial smoother of the given degree on x (SPEC §S9; tmp1, tmp2: work vectors shaped like x)."
+chebyshev!(x::DeviceVector, A::DeviceMatrix, b::DeviceVector, tmp1::DeviceVector, tmp2::DeviceVector, lmax::Real;
+           ratio::Real = 4.0, degree::Integer = 2) =
+    (check(ccall((:pamg_chebyshev, libpamg), Cint,
+                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint),
+                 A.ctx.h, A.h, x.h, b.h, tmp1.h, tmp2.h, lmax, ratio, degree)); x)
 "t = x + ω D⁻¹ (b - A x), r = b - A t (one fused pass where the matrix qualifies); returns whether it fused."
 function jacobi_residual!(t::DeviceVector, r::DeviceVector, A::DeviceMatrix, x::DeviceVector, b::DeviceVector, omega::Real)
     f = Ref{Cint}(0)
@@ -581,18 +594,22 @@ mutable struct VCycle
     omega::Vector{Float64}
     ainv::Matrix{Float64}            # coarsest inverse (reused when a tail joins a larger hierarchy)
     ncycles::Int                     # V-cycles per ldiv! (preconditioner use)
+    rho::Vector{Float64}             # the setup's spectral bounds per level (SPEC §S4.1; empty: unknown)
 end
 """
-    VCycle(ctx, A, P, R, omega, ainv; rep_level = length(A) - 1, rep_offsets = nothing, ncycles = 1)
+    VCycle(ctx, A, P, R, omega, ainv; rep_level = length(A) - 1, rep_offsets = nothing, ncycles = 1,
+           rho = Float64[])
 
 Device hierarchy from per-level device matrices (pamg_hier_create). `ainv` is the coarsest
 inverse (n_c × n_c, column-major = a Julia Matrix). Several ranks: levels ≥ rep_level are held
 whole on every rank (SPEC §S7); `rep_offsets` (nranks + 1, 0-based row offsets) say which rows
-of level rep_level each rank's restriction yields.
+of level rep_level each rank's restriction yields. `rho` (optional): the levels' bounds on the
+spectrum of D⁻¹A, the default `lmax` of `set_smoother!(M, :chebyshev)`.
 """
 function VCycle(ctx::Context, A::Vector{DeviceMatrix}, P::Vector{DeviceMatrix}, R::Vector{DeviceMatrix},
                 omega::Vector{Float64}, ainv::Matrix{Float64}; rep_level::Integer = length(A) - 1,
-                rep_offsets::Union{Nothing,Vector{Int64}} = nothing, ncycles::Integer = 1)
+                rep_offsets::Union{Nothing,Vector{Int64}} = nothing, ncycles::Integer = 1,
+                rho::Vector{Float64} = Float64[])
     L = length(A)
     length(P) == L - 1 && length(R) == L - 1 && length(omega) == L || throw(DimensionMismatch("levels"))
     pa = Ptr{Cvoid}[a.h for a in A]
@@ -604,7 +621,7 @@ function VCycle(ctx::Context, A::Vector{DeviceMatrix}, P::Vector{DeviceMatrix}, 
                  Ptr{Float64}, Cint, Ptr{Int64}, Ptr{Ptr{Cvoid}}),
                 ctx.h, L, pa, pp, pr, omega, size(ainv, 1), ainv, rep_level,
                 rep_offsets === nothing ? Ptr{Int64}(C_NULL) : rep_offsets, h))
-    M = VCycle(h[], ctx, A, P, R, omega, ainv, ncycles)
+    M = VCycle(h[], ctx, A, P, R, omega, ainv, ncycles, rho)
     finalizer(close, M)
 end
 function Base.close(M::VCycle)
@@ -617,6 +634,21 @@ set_graph!(M::VCycle, enable::Bool) =
     check(ccall((:pamg_hier_set_graph, libpamg), Cint, (Ptr{Cvoid}, Cint), M.h, enable))
 set_sweeps!(M::VCycle, nu1::Integer, nu2::Integer) =
     check(ccall((:pamg_hier_set_sweeps, libpamg), Cint, (Ptr{Cvoid}, Cint, Cint), M.h, nu1, nu2))
+"""
+    set_smoother!(M, kind; ratio = 4.0, lmax = M.rho)
+
+The V-cycle's smoother: `:jacobi` (default) or `:chebyshev` — one polynomial of degree nu1 before
+and nu2 after the coarse correction (`set_sweeps!` gives the degrees), level l over
+[lmax[l] / ratio, lmax[l]] (SPEC §S9). `lmax` needs an entry for every level but the coarsest.
+"""
+function set_smoother!(M::VCycle, kind::Symbol; ratio::Real = 4.0, lmax::Vector{Float64} = M.rho)
+    k = Dict(:jacobi => 0, :chebyshev => 1)[kind]
+    nl = length(M.A) - 1
+    k == 0 || length(lmax) >= nl || throw(DimensionMismatch("set_smoother!: lmax needs $nl entries"))
+    check(ccall((:pamg_hier_set_smoother, libpamg), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cdouble), M.h, k,
+                k == 0 || nl == 0 ? Ptr{Float64}(C_NULL) : lmax, ratio))
+    M
+end
 "Level-0 numbering of a hierarchy uploaded with locality permutations (1-based; nothing = none)."
 function set_perm!(M::VCycle, perm::Union{Nothing,AbstractVector{<:Integer}})
     p = perm === nothing ? Int64[] : Int64.(perm) .- 1
@@ -671,11 +703,12 @@ hierarchy, every level but the coarsest uploaded through its locality order (`re
 function setup_hierarchy(ctx::Context, A0::HostCSR; theta::Real = 0.02, max_coarse::Integer = 1000,
                          max_levels::Integer = 20, gpu_products::Bool = true, ncycles::Integer = 1,
                          reorder::Symbol = :auto)
-    A, P, R, omega = HostCSR[A0], HostCSR[], HostCSR[], Float64[]
+    A, P, R, omega, rhos = HostCSR[A0], HostCSR[], HostCSR[], Float64[], Float64[]
     while true
         rho = Ref{Cdouble}(0.0)
         check(ccall((:pamg_setup_gershgorin, libpamg), Cint, (Ptr{Cvoid}, Int64, Ptr{Cdouble}), A[end].h, 0, rho))
         push!(omega, 4.0 / (3.0 * rho[]))
+        push!(rhos, rho[])
         n = size(A[end], 1)
         (n <= max_coarse || length(A) >= max_levels) && break
         agg, nagg = Vector{Int32}(undef, n + 1), Ref{Int64}(0)
@@ -721,7 +754,7 @@ function setup_hierarchy(ctx::Context, A0::HostCSR; theta::Real = 0.02, max_coar
     dA = [DeviceMatrix(ctx, A[l]; row_perm = perm[l], col_perm = perm[l]) for l in 1:L]
     dP = [DeviceMatrix(ctx, P[l]; row_perm = perm[l], col_perm = perm[l+1]) for l in 1:L-1]
     dR = [DeviceMatrix(ctx, R[l]; row_perm = perm[l+1], col_perm = perm[l]) for l in 1:L-1]
-    M = VCycle(ctx, dA, dP, dR, omega, ainv; ncycles = ncycles)
+    M = VCycle(ctx, dA, dP, dR, omega, ainv; ncycles = ncycles, rho = rhos)
     perm[1] === nothing || set_perm!(M, perm[1])
     M
 end

@@ -86,10 +86,13 @@ SIGNATURES = {
     "pamg_residual": [vp, vp, vp, vp, vp, pdbl],
     "pamg_jacobi": [vp, vp, vp, vp, vp, dbl, i32],
     "pamg_jacobi_residual": [vp, vp, vp, vp, vp, vp, dbl, pi32],
+    "pamg_chebyshev_coeffs": [dbl, dbl, i32, vp, vp],
+    "pamg_chebyshev": [vp, vp, vp, vp, vp, vp, dbl, dbl, i32],
     "pamg_hier_create": [vp, i32, vp, vp, vp, vp, i64, vp, i32, vp, pvp],
     "pamg_hier_destroy": [vp],
     "pamg_hier_set_graph": [vp, i32],
     "pamg_hier_set_sweeps": [vp, i32, i32],
+    "pamg_hier_set_smoother": [vp, i32, vp, dbl],
     "pamg_hier_set_perm": [vp, i64, vp],
     "pamg_hier_graph_state": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pamg_vcycle": [vp, vp, vp, vp, i32, vp],

@@ -54,10 +54,26 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     return v;
 }
 
+// OP_JACOBI and OP_CHEB capture the row's diagonal on the way (the in-tile / in-row search).
+template <int OP>
+constexpr bool kDiagOp = OP == OP_JACOBI || OP == OP_CHEB;
+
+// The Chebyshev step k >= 1 (SPEC §S9) from the row's residual u = b_i - s: seven roundings, none
+// fused (-ffp-contract=off). xo is xold_i, +0.0 where the step follows a zero guess.
+__device__ __forceinline__ double cheb_step(double u, double xi, double xo, double d, double c1, double c2) {
+    const double v = c2 * u;
+    const double w = v / d;
+    const double e = xi - xo;
+    const double q = c1 * e;
+    const double t = q + w;
+    return xi + t;
+}
+
 template <int OP>
 __device__ __forceinline__ void epilogue(int r, double s, const double* __restrict__ x,
                                          const double* __restrict__ b, double* __restrict__ y,
-                                         double omega, double d) {
+                                         double omega, double d, double c1 = 0.0,
+                                         const double* __restrict__ xold = nullptr) {
     if constexpr (OP == OP_SPMV) {
         y[r] = s;
     } else if constexpr (OP == OP_RESID) {
@@ -67,6 +83,8 @@ __device__ __forceinline__ void epilogue(int r, double s, const double* __restri
         const double v = omega * u;
         const double w = v / d;
         y[r] = x[r] + w;
+    } else if constexpr (OP == OP_CHEB) {
+        y[r] = cheb_step(b[r] - s, x[r], xold ? xold[r] : 0.0, d, c1, omega);
     } else {
         y[r] = y[r] + s;
     }
@@ -136,7 +154,8 @@ __global__ __launch_bounds__(kBlock) void k_rows_tile2(
     const int* __restrict__ tbase = nullptr, const uint8_t* __restrict__ vidx = nullptr,
     const double* __restrict__ vtab = nullptr, const uint8_t* __restrict__ rlen = nullptr,
     const uint8_t* __restrict__ cidx = nullptr, const int* __restrict__ ctab = nullptr,
-    int ctab_n = 0, const uint16_t* __restrict__ anc16 = nullptr, const int* __restrict__ abase = nullptr) {
+    int ctab_n = 0, const uint16_t* __restrict__ anc16 = nullptr, const int* __restrict__ abase = nullptr,
+    double c1 = 0.0, const double* __restrict__ xold = nullptr) {
     // PT: per-tile dictionary — this tile's table is ctab[bid * ctab_n ...]; ANC: columns are
     // the row's anchor (abase[tile] + anc16[row]) + table[index] instead of row + table[index]
     static_assert(!PT || CD != 0, "per-tile tables are column dictionaries");
@@ -150,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_tile2(
     static_assert(G >= 1 && TNNZ % (4 * BS) == 0, "tile budget must be a multiple of 4 x block");
     __shared__ __attribute__((aligned(16))) double lprod[TNNZ + 8];
     __shared__ int lrp[kTileRows + 1];
-    __shared__ double ldiag[OP == OP_JACOBI ? kTileRows : 1];
+    __shared__ double ldiag[kDiagOp<OP> ? kTileRows : 1];
     // RL8: row lengths are 8-bit (1 B/row instead of a 4-B row pointer); the row starts are
     // rebuilt from the tile's first nonzero by a wave-level scan + the wave totals (lwt)
     static_assert(kTileRows <= BS, "one row per lane");
@@ -212,11 +231,12 @@ __global__ __launch_bounds__(kBlock) void k_rows_tile2(
     }
     // one row per lane: the epilogue's own-row operands (b, old x, y), so their latency
     // hides under the stream instead of trailing the LDS phase
-    double pb = 0.0, px = 0.0, py = 0.0;
+    double pb = 0.0, px = 0.0, py = 0.0, pxo = 0.0;
     {
         const int r = r0 + lr;
-        if constexpr (OP == OP_RESID || OP == OP_JACOBI) pb = b[r];
-        if constexpr (OP == OP_JACOBI) px = x[r];
+        if constexpr (OP == OP_RESID || kDiagOp<OP>) pb = b[r];
+        if constexpr (kDiagOp<OP>) px = x[r];
+        if constexpr (OP == OP_CHEB) pxo = xold ? xold[r] : 0.0;
         if constexpr (OP == OP_PROLONG) py = y[r];
     }
     asm volatile("" ::: "memory");  // keep the loads above ahead of the value stream
@@ -271,7 +291,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_tile2(
             }
             c4[j] = make_int4(cc[0], cc[1], cc[2], cc[3]);
         }
-    } else if constexpr (OP == OP_JACOBI) {
+    } else if constexpr (kDiagOp<OP>) {
         __syncthreads();
         if constexpr (RL8) {  // the in-tile diagonal search needs every row's bounds
             const int base = rl_base();
@@ -313,7 +333,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_tile2(
             const int k = g + e;
             const bool ok = (k >= z0) & (k < z1);
             p[e] = ok ? vv[e] * xv[j][e] : 0.0;
-            if constexpr (OP == OP_JACOBI) {
+            if constexpr (kDiagOp<OP>) {
                 const int rl = cc[e] - r0;
                 if constexpr (CD != 0) {
                     // the diagonal is the entry whose column is its own row
@@ -350,6 +370,8 @@ __global__ __launch_bounds__(kBlock) void k_rows_tile2(
         const double v = omega * u;
         const double w = v / ldiag[tid < nr ? tid : 0];
         out = px + w;
+    } else if constexpr (OP == OP_CHEB) {
+        out = cheb_step(pb - s, px, pxo, ldiag[tid < nr ? tid : 0], c1, omega);
     } else {
         out = py + s;
     }
@@ -385,7 +407,8 @@ __global__ __launch_bounds__(kBlock) void k_rows_tm(
     const uint8_t* __restrict__ trlen, int rs, const int* __restrict__ ctab, int ctab_n,
     const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y,
     double omega, const int* __restrict__ tanc = nullptr, const XStage xst = XStage{},
-    const uint8_t* __restrict__ tvidx = nullptr, const double* __restrict__ tvtab = nullptr, int vt = 0) {
+    const uint8_t* __restrict__ tvidx = nullptr, const double* __restrict__ tvtab = nullptr, int vt = 0,
+    double c1 = 0.0, const double* __restrict__ xold = nullptr) {
     // ANC (anchored dictionary): column = the row's first column (slot anchors, tanc) +
     // table[index] instead of row + table[index]
     static_assert(!ANC || CD != 0, "anchored columns are dictionary columns");
@@ -396,7 +419,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_tm(
     constexpr int G = TNNZ / (4 * BS);
     static_assert(G >= 1 && TNNZ % (4 * BS) == 0, "tile budget must be a multiple of 4 x block");
     __shared__ __attribute__((aligned(16))) double lprod[TNNZ + 8];
-    __shared__ double ldiag[OP == OP_JACOBI ? BS : 1];
+    __shared__ double ldiag[kDiagOp<OP> ? BS : 1];
     __shared__ int lwt[BS / 64];
     // XS keeps only the table's LDS positions (kXsIoff + index): 16 / 128 entries, so the
     // staged runs fit beside Jacobi's arrays at 8 blocks per CU
@@ -449,11 +472,12 @@ __global__ __launch_bounds__(kBlock) void k_rows_tm(
             cn[j] = *reinterpret_cast<const uint32_t*>(tchi + q);
         }
     }
-    double pb = 0.0, px = 0.0, py = 0.0;
+    double pb = 0.0, px = 0.0, py = 0.0, pxo = 0.0;
     {
         const int r = r0 + (tid < nr ? tid : 0);  // padding tiles are (0, 0, 0, 0): row 0
-        if constexpr (OP == OP_RESID || OP == OP_JACOBI) pb = b[r];
-        if constexpr (OP == OP_JACOBI) px = x[r];
+        if constexpr (OP == OP_RESID || kDiagOp<OP>) pb = b[r];
+        if constexpr (kDiagOp<OP>) px = x[r];
+        if constexpr (OP == OP_CHEB) pxo = xold ? xold[r] : 0.0;
         if constexpr (OP == OP_PROLONG) py = y[r];
     }
     double xsv[XS ? kXsMaxClusters : 1];
@@ -506,7 +530,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_tm(
     // Per-position row ids are needed for dictionary columns (row + offset) and for Jacobi's
     // in-tile diagonal; 24-bit SpMV / residual / prolongate-add skip them, so their gathers
     // follow the stream loads with no barrier in between.
-    constexpr bool NEED_ROWS = CD != 0 || OP == OP_JACOBI;
+    constexpr bool NEED_ROWS = CD != 0 || kDiagOp<OP>;
     int re = 0;
     if constexpr (VD8 && !NEED_ROWS) __syncthreads();  // lvt
     if constexpr (NEED_ROWS) {
@@ -573,7 +597,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_tm(
         for (int e = 0; e < 4; ++e) {
             const bool ok = q + e < cnt;
             p[e] = ok ? vv[e] * xv[j][e] : 0.0;
-            if constexpr (OP == OP_JACOBI) {
+            if constexpr (kDiagOp<OP>) {
                 const int rl = (int)((rw >> (8 * e)) & 255u);
                 if (ok && (XS ? cc[j][e] == xst.zix : cc[j][e] - r0 == rl)) ldiag[rl] = vv[e];
             }
@@ -596,6 +620,8 @@ __global__ __launch_bounds__(kBlock) void k_rows_tm(
         const double v = omega * u;
         const double w = v / ldiag[tid < nr ? tid : 0];
         out = px + w;
+    } else if constexpr (OP == OP_CHEB) {
+        out = cheb_step(pb - s, px, pxo, ldiag[tid < nr ? tid : 0], c1, omega);
     } else {
         out = py + s;
     }
@@ -1569,7 +1595,8 @@ __global__ __launch_bounds__(kZmThreads) void k_sym_zm(int nrows, const uint8_t*
                                                        const double* __restrict__ vtab, const uint32_t* __restrict__ mtab,
                                                        int nv, const TbGeom g, const double* __restrict__ x,
                                                        const double* __restrict__ b, double* __restrict__ y,
-                                                       double omega) {
+                                                       double omega, double c1 = 0.0,
+                                                       const double* __restrict__ xold = nullptr) {
     __shared__ __attribute__((aligned(16))) double2 sx[2][kTbY + 2][kZmW];
     __shared__ __attribute__((aligned(16))) uint16_t sid[2][kTbY + 2][kZmW];
     __shared__ __attribute__((aligned(16))) SymTab<3> tab;
@@ -1601,11 +1628,16 @@ __global__ __launch_bounds__(kZmThreads) void k_sym_zm(int nrows, const uint8_t*
         if constexpr (OP == OP_SPMV) return make_double2(0.0, 0.0);
         return q < g.nz ? *reinterpret_cast<const double2*>(b + (int64_t)q * M + ixy[h]) : make_double2(0.0, 0.0);
     };
+    // OP_CHEB: x_{k-1} of the own rows, one more coalesced stream beside b (null: zeros, uniform)
+    auto ldxo = [&](int q, int h) {
+        return xold && q < g.nz ? *reinterpret_cast<const double2*>(xold + (int64_t)q * M + ixy[h])
+                                : make_double2(0.0, 0.0);
+    };
     // plane rings indexed by compile-time constants in the 4-way unrolled loop (renaming: no copy
     // of a register with a load in flight, see k_sym_zc): X[(u + j) & 3][h] = x of plane k-1+j
     // (j = 3: k+2 in flight), ID[(u + j) & 3][h] = ids of plane k-1+j (j = 2: k+1 in flight),
-    // B[(u + j) & 1][h] = b of plane k+j, HL[(u + j) & 1] = halo of plane k+j
-    double2 X[4][2], B[2][2];
+    // B[(u + j) & 1][h] = b of plane k+j (XO: xold, OP_CHEB), HL[(u + j) & 1] = halo of plane k+j
+    double2 X[4][2], B[2][2], XO[2][2];
     uint32_t ID[4][2];
     ZmHalo HL[2];
 #pragma unroll
@@ -1616,6 +1648,7 @@ __global__ __launch_bounds__(kZmThreads) void k_sym_zm(int nrows, const uint8_t*
         ID[0][h] = ldid(z0 - 1, h);
         ID[1][h] = ldid(z0, h);
         B[0][h] = ldb(z0, h);
+        if constexpr (OP == OP_CHEB) XO[0][h] = ldxo(z0, h);
     }
     zm_halo_load(HL[0], x, tid, x0, y0, g.nx, g.ny, g.nz, M, z0);
     for (int kb = z0; kb < z1; kb += 4) {
@@ -1632,6 +1665,8 @@ __global__ __launch_bounds__(kZmThreads) void k_sym_zm(int nrows, const uint8_t*
             uint32_t(&idn)[2] = ID[(u + 2) & 3];
             double2(&bc)[2] = B[u & 1];
             double2(&bn)[2] = B[(u + 1) & 1];
+            [[maybe_unused]] double2(&xoc)[2] = XO[u & 1];
+            [[maybe_unused]] double2(&xon)[2] = XO[(u + 1) & 1];
             ZmHalo& hc = HL[u & 1];
             ZmHalo& hn = HL[(u + 1) & 1];
             const int sl = k & 1;
@@ -1647,6 +1682,7 @@ __global__ __launch_bounds__(kZmThreads) void k_sym_zm(int nrows, const uint8_t*
                 xn[h] = ldx(k + 2, h);
                 idn[h] = ldid(k + 1, h);
                 bn[h] = ldb(k + 1, h);
+                if constexpr (OP == OP_CHEB) xon[h] = ldxo(k + 1, h);
             }
             zm_halo_load(hn, x, tid, x0, y0, g.nx, g.ny, g.nz, M, k + 1);
             __syncthreads();  // plane k's slot; the slot stored next step was last read a step ago
@@ -1685,6 +1721,14 @@ __global__ __launch_bounds__(kZmThreads) void k_sym_zm(int nrows, const uint8_t*
                         o[r] = sacc;
                     } else if constexpr (OP == OP_RESID) {
                         o[r] = bv[r] - sacc;
+                    } else if constexpr (OP == OP_CHEB) {  // (SPEC §S9 step k >= 1; w as Jacobi's, div_rn)
+                        const double u2 = bv[r] - sacc;
+                        const double vv = omega * u2;
+                        const double w = div_rn(vv, v[3], tab.r[tc]);
+                        const double e = xv[r][3] - (r == 0 ? xoc[h].x : xoc[h].y);
+                        const double q2 = c1 * e;
+                        const double t2 = q2 + w;
+                        o[r] = xv[r][3] + t2;
                     } else {
                         const double u2 = bv[r] - sacc;
                         const double w = omega * u2;
@@ -1716,7 +1760,7 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ell(int nrows, const int* __
                                                         const int* __restrict__ otab, const double* __restrict__ vtab,
                                                         int ngroups, const double* __restrict__ x,
                                                         const double* __restrict__ b, double* __restrict__ y,
-                                                        double omega) {
+                                                        double omega, double c1, const double* __restrict__ xold) {
     __shared__ int lo[256];
     __shared__ double lv[256];
     const int per = (ngroups + 7) / 8;
@@ -1736,10 +1780,11 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ell(int nrows, const int* __
     const uint32_t* __restrict__ vp = (PAIR ? cw : vw) + sm.x + lane;
     const int nq = (sm.y + 3) >> 2;
     uint32_t c4 = nq > 0 ? cp[0] : 0u, v4 = PAIR ? 0u : (nq > 0 ? vp[0] : 0u);
-    double pb = 0.0, px = 0.0, py = 0.0;
-    if constexpr (OP == OP_RESID || OP == OP_JACOBI) pb = b[ic];
-    if constexpr (OP == OP_JACOBI) px = x[ic];
+    double pb = 0.0, px = 0.0, py = 0.0, pxo = 0.0;
+    if constexpr (OP == OP_RESID || kDiagOp<OP>) pb = b[ic];
+    if constexpr (kDiagOp<OP>) px = x[ic];
     if constexpr (OP == OP_PROLONG) py = y[ic];
+    if constexpr (OP == OP_CHEB) pxo = xold ? xold[ic] : 0.0;
     const int ot = gm.x + (tid < gm.y ? tid : 0), vt = gm.z + (tid < gm.w ? tid : 0);
     const int otv = otab[ot];
     const double vtv = vtab[vt];
@@ -1768,7 +1813,7 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ell(int nrows, const int* __
             const double p = vv[e] * xv[e];
             const double t = s + p;
             s = ok ? t : s;
-            if constexpr (OP == OP_JACOBI) dg = ok && of[e] == 0 ? vv[e] : dg;
+            if constexpr (kDiagOp<OP>) dg = ok && of[e] == 0 ? vv[e] : dg;
         }
     }
     double out;
@@ -1781,6 +1826,8 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ell(int nrows, const int* __
         const double v = omega * u;
         const double w = v / dg;
         out = px + w;
+    } else if constexpr (OP == OP_CHEB) {
+        out = cheb_step(pb - s, px, pxo, dg, c1, omega);
     } else {
         out = py + s;
     }
@@ -1851,7 +1898,8 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
                                                          const uint16_t* __restrict__ lofs, int win, int gather_all,
                                                          int ngroups, const double* __restrict__ x,
                                                          const double* __restrict__ b, double* __restrict__ y,
-                                                         double omega) {
+                                                         double omega, double c1 = 0.0,
+                                                         const double* __restrict__ xold = nullptr) {
     extern __shared__ double ellw_lds[];
     double* lx = ellw_lds;
     double* lv = ellw_lds + win;
@@ -1878,13 +1926,14 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
     const int2 sm = smeta[slice >= 0 ? slice : 0];
     const int nq = slice >= 0 ? (sm.y + 3) >> 2 : 0;
     const uint32_t* __restrict__ cp = cw + sm.x + lane;
-    double pb = 0.0, px = 0.0, py = 0.0;
-    if constexpr (OP == OP_RESID || OP == OP_JACOBI) pb = b[ic];
-    if constexpr (OP == OP_JACOBI) px = x[ic];
+    double pb = 0.0, px = 0.0, py = 0.0, pxo = 0.0;
+    if constexpr (OP == OP_RESID || kDiagOp<OP>) pb = b[ic];
+    if constexpr (kDiagOp<OP>) px = x[ic];
     if constexpr (OP == OP_PROLONG) py = y[ic];
+    if constexpr (OP == OP_CHEB) pxo = xold ? xold[ic] : 0.0;
     uint32_t dkw = 0u;
     int dk = 255;
-    if constexpr (OP == OP_JACOBI) {
+    if constexpr (kDiagOp<OP>) {
         dk = in ? (int)dpos[ic] : 255;
         dkw = cw[dk != 255 ? sm.x + lane + (dk >> 2) * kEllW : 0];
     }
@@ -1936,6 +1985,9 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
         const double dg = dk != 255 ? lv[(dkw >> (8 * (dk & 3))) & 255u] : 0.0;
         const double wq = v / dg;
         out = px + wq;
+    } else if constexpr (OP == OP_CHEB) {
+        const double dg = dk != 255 ? lv[(dkw >> (8 * (dk & 3))) & 255u] : 0.0;
+        out = cheb_step(pb - s, px, pxo, dg, c1, omega);
     } else {
         out = py + s;
     }
@@ -2180,7 +2232,7 @@ template <int OP>
 __global__ __launch_bounds__(kBlock) void k_rows_long(
     const int* __restrict__ rows, const int* __restrict__ rowptr, const int* __restrict__ col,
     const double* __restrict__ val, const double* __restrict__ x, const double* __restrict__ b,
-    double* __restrict__ y, double omega) {
+    double* __restrict__ y, double omega, double c1 = 0.0, const double* __restrict__ xold = nullptr) {
     __shared__ double lprod[kBlock + 8];  // + 8: row_sum_lds reads (and discards) up to 7 past the end
     __shared__ double ldiag;
     const int tid = threadIdx.x;
@@ -2194,7 +2246,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_long(
             const int c = col[k];
             const double v = val[k];
             p = v * x[c];
-            if constexpr (OP == OP_JACOBI) {
+            if constexpr (kDiagOp<OP>) {
                 if (c == r) ldiag = v;
             }
         }
@@ -2203,7 +2255,29 @@ __global__ __launch_bounds__(kBlock) void k_rows_long(
         if (tid == 0) s = row_sum_lds(lprod, 0, min(kBlock, z1 - base), s);
         __syncthreads();
     }
-    if (tid == 0) epilogue<OP>(r, s, x, b, y, omega, OP == OP_JACOBI ? ldiag : 0.0);
+    if constexpr (OP == OP_CHEB) {
+        if (tid == 0) epilogue<OP>(r, s, x, b, y, omega, ldiag, c1, xold);
+    } else {
+        if (tid == 0) epilogue<OP>(r, s, x, b, y, omega, OP == OP_JACOBI ? ldiag : 0.0);
+    }
+}
+
+// The Chebyshev step of the symmetric layouts' older kernels (k_rows_sym / sym2 / symd), which run
+// OP_RESID into y first: y_i = cheb_step(y_i, ...) in place over the rows of the set — u is the
+// residual, so the seven roundings are the native kernels' (SPEC §S9). In-set flag: the row's mask
+// (mask_bytes 1 | 2) or, with the row-class dictionary (ids != null), its class's mask.
+__global__ __launch_bounds__(kBlock) void k_cheb_update(int64_t n, const uint8_t* __restrict__ mask, int mask_bytes,
+                                                        const uint8_t* __restrict__ ids,
+                                                        const uint32_t* __restrict__ mtab, uint32_t in_flag,
+                                                        const double* __restrict__ diag, const double* __restrict__ x,
+                                                        const double* __restrict__ xold, double* __restrict__ y,
+                                                        double c1, double c2) {
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const uint32_t m = ids ? mtab[ids[i]]
+                               : (mask_bytes == 1 ? (uint32_t)mask[i] : (uint32_t)reinterpret_cast<const uint16_t*>(mask)[i]);
+        if (!(m & in_flag)) continue;
+        y[i] = cheb_step(y[i], x[i], xold ? xold[i] : 0.0, diag[i], c1, c2);
+    }
 }
 
 __global__ void k_jacobi_zero(int64_t n, const double* __restrict__ b,
@@ -2357,108 +2431,149 @@ inline int grid_for(int64_t n, int cap = 8192) {
     return (int)(g < cap ? g : cap);
 }
 
+// OP_CHEB's extra operands (its c2 is the launchers' omega); empty for every other operation
+struct Cheb {
+    double c1 = 0.0;
+    const double* xold = nullptr;
+};
+
 // descriptor kernel with column dictionaries: global tables, or per-tile (PT) ones, anchored or not
 template <int OP, int TNNZ, bool PT>
 void launch_tile2_cd(const pamg_mat& A, const TileSet& ts, const double* x, const double* b, double* y,
-                     double omega, hipStream_t s) {
+                     double omega, hipStream_t s, Cheb ch) {
     const int n = ts.n_short;
     if (PT && ts.anc) {
         if (ts.cd == 4)
             k_rows_tile2<OP, TNNZ, false, false, true, 4, true, true><<<n, kBlock, 0, s>>>(
                 ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y, omega, nullptr, nullptr, nullptr, nullptr, nullptr,
-                A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n, A.d_anc16, ts.d_abase);
+                A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n, A.d_anc16, ts.d_abase, ch.c1, ch.xold);
         else
             k_rows_tile2<OP, TNNZ, false, false, true, 8, true, true><<<n, kBlock, 0, s>>>(
                 ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y, omega, nullptr, nullptr, nullptr, nullptr, nullptr,
-                A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n, A.d_anc16, ts.d_abase);
+                A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n, A.d_anc16, ts.d_abase, ch.c1, ch.xold);
     } else if (ts.cd == 4) {
         k_rows_tile2<OP, TNNZ, false, false, true, 4, PT><<<n, kBlock, 0, s>>>(
             ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y, omega, nullptr, nullptr, nullptr, nullptr, nullptr,
-            A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n);
+            A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n, nullptr, nullptr, ch.c1, ch.xold);
     } else {
         k_rows_tile2<OP, TNNZ, false, false, true, 8, PT><<<n, kBlock, 0, s>>>(
             ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y, omega, nullptr, nullptr, nullptr, nullptr, nullptr,
-            A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n);
+            A.d_rlen, A.d_cidx, ts.d_ctab, ts.ctab_n, nullptr, nullptr, ch.c1, ch.xold);
     }
 }
 
 template <int OP, int TNNZ, bool VD8>
 void launch_tm(const pamg_mat& A, const TileSet& ts, const double* x, const double* b, double* y, double omega,
-               hipStream_t s) {
+               hipStream_t s, Cheb ch) {
     (void)A;
     const int n = ts.n_short;
     if (ts.anc && ts.cd == 4)
         k_rows_tm<OP, TNNZ, 4, true, false, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx, nullptr, nullptr,
                                                          nullptr, ts.d_tm_rlen, ts.tm_rs, ts.d_ctab, ts.ctab_n,
-                                                         x, b, y, omega, ts.d_tm_anc, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                         x, b, y, omega, ts.d_tm_anc, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.anc)
         k_rows_tm<OP, TNNZ, 8, true, false, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx, nullptr, nullptr,
                                                          nullptr, ts.d_tm_rlen, ts.tm_rs, ts.d_ctab, ts.ctab_n,
-                                                         x, b, y, omega, ts.d_tm_anc, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                         x, b, y, omega, ts.d_tm_anc, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.pt && ts.cd == 4)
         k_rows_tm<OP, TNNZ, 4, false, false, true, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx,
                                                                       nullptr, nullptr, nullptr, ts.d_tm_rlen,
                                                                       ts.tm_rs, ts.d_ctab, ts.ctab_n, x, b, y,
-                                                                      omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                                      omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.pt)
         k_rows_tm<OP, TNNZ, 8, false, false, true, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx,
                                                                       nullptr, nullptr, nullptr, ts.d_tm_rlen,
                                                                       ts.tm_rs, ts.d_ctab, ts.ctab_n, x, b, y,
-                                                                      omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                                      omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.xs && ts.cd == 4)
         k_rows_tm<OP, TNNZ, 4, false, true, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx, nullptr,
                                                                nullptr, nullptr, ts.d_tm_rlen, ts.tm_rs, ts.d_ctab,
-                                                               ts.ctab_n, x, b, y, omega, nullptr, ts.xst, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                               ts.ctab_n, x, b, y, omega, nullptr, ts.xst, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.xs)
         k_rows_tm<OP, TNNZ, 8, false, true, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx, nullptr,
                                                                nullptr, nullptr, ts.d_tm_rlen, ts.tm_rs, ts.d_ctab,
-                                                               ts.ctab_n, x, b, y, omega, nullptr, ts.xst, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                               ts.ctab_n, x, b, y, omega, nullptr, ts.xst, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.cd == 4)
         k_rows_tm<OP, TNNZ, 4, false, false, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx, nullptr, nullptr,
                                                    nullptr, ts.d_tm_rlen, ts.tm_rs, ts.d_ctab, ts.ctab_n, x,
-                                                   b, y, omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                   b, y, omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else if (ts.cd == 8)
         k_rows_tm<OP, TNNZ, 8, false, false, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, ts.d_tm_cidx, nullptr, nullptr,
                                                    nullptr, ts.d_tm_rlen, ts.tm_rs, ts.d_ctab, ts.ctab_n, x,
-                                                   b, y, omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                   b, y, omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
     else
         k_rows_tm<OP, TNNZ, 0, false, false, false, VD8><<<n, kBlock, 0, s>>>(ts.d_short, ts.d_tm_val, nullptr, ts.d_tm_clo,
                                                    ts.d_tm_chi, ts.d_base, ts.d_tm_rlen, ts.tm_rs, nullptr,
-                                                   0, x, b, y, omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt);
+                                                   0, x, b, y, omega, nullptr, XStage{}, ts.d_tm_vidx, ts.d_tm_vtab, ts.tm_vt, ch.c1, ch.xold);
 }
 
 template <int OP, int TNNZ>
 void launch_tile(const pamg_mat& A, const TileSet& ts, const double* x, const double* b,
-                 double* y, double omega, hipStream_t s) {
+                 double* y, double omega, hipStream_t s, Cheb ch) {
     const int n = ts.n_short;
+    // the descriptor kernel's unused dictionary arguments, spelled out up to c1 / xold
+    const uint8_t* const no8 = nullptr;
+    const int* const no32 = nullptr;
+    const uint16_t* const no16 = nullptr;
+    const double* const nod = nullptr;
     if (ts.tm) {
         if (ts.tm_vt)
-            launch_tm<OP, TNNZ, true>(A, ts, x, b, y, omega, s);
+            launch_tm<OP, TNNZ, true>(A, ts, x, b, y, omega, s, ch);
         else
-            launch_tm<OP, TNNZ, false>(A, ts, x, b, y, omega, s);
+            launch_tm<OP, TNNZ, false>(A, ts, x, b, y, omega, s, ch);
     } else if (ts.cd && A.d_cidx && ts.rl8 && A.d_rlen) {
         if (ts.pt)
-            launch_tile2_cd<OP, TNNZ, true>(A, ts, x, b, y, omega, s);
+            launch_tile2_cd<OP, TNNZ, true>(A, ts, x, b, y, omega, s, ch);
         else
-            launch_tile2_cd<OP, TNNZ, false>(A, ts, x, b, y, omega, s);
+            launch_tile2_cd<OP, TNNZ, false>(A, ts, x, b, y, omega, s, ch);
     } else if (ts.c24 && A.d_clo && ts.vd && A.d_vidx && ts.rl8 && A.d_rlen) {
         k_rows_tile2<OP, TNNZ, true, true, true><<<n, kBlock, 0, s>>>(ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b,
                                                                      y, omega, A.d_clo, A.d_chi, ts.d_base,
-                                                                     A.d_vidx, ts.d_vtab, A.d_rlen);
+                                                                     A.d_vidx, ts.d_vtab, A.d_rlen, no8, no32, 0,
+                                                                     no16, no32, ch.c1, ch.xold);
     } else if (ts.c24 && A.d_clo && ts.vd && A.d_vidx) {
         k_rows_tile2<OP, TNNZ, true, true><<<n, kBlock, 0, s>>>(ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y,
                                                                omega, A.d_clo, A.d_chi, ts.d_base, A.d_vidx,
-                                                               ts.d_vtab);
+                                                               ts.d_vtab, no8, no8, no32, 0, no16, no32, ch.c1,
+                                                               ch.xold);
     } else if (ts.c24 && A.d_clo && ts.rl8 && A.d_rlen) {
         k_rows_tile2<OP, TNNZ, true, false, true><<<n, kBlock, 0, s>>>(ts.d_short, A.d_rowptr, A.d_col, A.d_val,
                                                                       x, b, y, omega, A.d_clo, A.d_chi,
-                                                                      ts.d_base, nullptr, nullptr, A.d_rlen);
+                                                                      ts.d_base, no8, nod, A.d_rlen, no8, no32, 0,
+                                                                      no16, no32, ch.c1, ch.xold);
     } else if (ts.c24 && A.d_clo) {
         k_rows_tile2<OP, TNNZ, true><<<n, kBlock, 0, s>>>(ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y,
-                                                         omega, A.d_clo, A.d_chi, ts.d_base);
+                                                         omega, A.d_clo, A.d_chi, ts.d_base, no8, nod, no8, no8,
+                                                         no32, 0, no16, no32, ch.c1, ch.xold);
     } else {
-        k_rows_tile2<OP, TNNZ><<<n, kBlock, 0, s>>>(ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y, omega);
+        k_rows_tile2<OP, TNNZ><<<n, kBlock, 0, s>>>(ts.d_short, A.d_rowptr, A.d_col, A.d_val, x, b, y, omega, no16,
+                                                    no8, no32, no8, nod, no8, no8, no32, 0, no16, no32, ch.c1,
+                                                    ch.xold);
     }
+}
+
+// The z-marching sweep of a whole one-part grid operator (Options::sym_zm), where the layout allows
+// it (plane0 == 0 and the bands covering every row: not a plane window of launch_sym_planes);
+// false: not taken
+template <int OP>
+bool launch_sym_zm(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s,
+                   Cheb ch = Cheb{}) {
+    const SymDia& sd = A.sym;
+    if (!(sd.nu == 3 && sd.vd_n && sd.tb_ok && !sd.tb_part && options().sym_zm && sd.plane0 == 0 &&
+          (int64_t)sd.nbands * sd.band >= A.nrows && A.nrows == (int64_t)sd.tb.nx * sd.tb.ny * sd.tb.nz &&
+          A.nrows % 2 == 0))
+        return false;
+    TbGeom g = sd.tb;  // (y-fastest tiles: x-fastest measured +-2 %, profiles/r05_l/)
+    const int tiles = g.tiles_x * g.tiles_y;
+    // z chunks: ~4 workgroups per CU (1024), chunks of >= 16 planes; zm_chunks overrides
+    int zc = options().zm_chunks > 0 ? options().zm_chunks : std::min((1024 + tiles - 1) / tiles, g.nz / 16);
+    zc = std::max(1, std::min(zc, g.nz));
+    g.zlen = (g.nz + zc - 1) / zc;
+    g.zchunks = (g.nz + g.zlen - 1) / g.zlen;
+    const int gr = (tiles * g.zchunks + 7) / 8 * 8;
+    k_sym_zm<OP><<<gr, kZmThreads, 0, s>>>((int)A.nrows, sd.d_tid, sd.d_vtab, sd.d_mtab, sd.vd_n, g, x, b, y, omega,
+                                           ch.c1, ch.xold);
+    return true;
 }
 
 template <int OP, int NU>
@@ -2466,23 +2581,7 @@ void launch_sym_nu(const pamg_mat& A, const double* x, const double* b, double* 
     const SymDia& sd = A.sym;
     const int grid = sd.nbands * 8 * sd.eighth;
     if constexpr (NU == 3) {
-        // the whole one-part grid operator: the z-marching sweep (Options::sym_zm)
-        // (plane0 == 0 and the bands covering every row: not a plane window of launch_sym_planes)
-        if (sd.vd_n && sd.tb_ok && !sd.tb_part && options().sym_zm && sd.plane0 == 0 &&
-            (int64_t)sd.nbands * sd.band >= A.nrows && A.nrows == (int64_t)sd.tb.nx * sd.tb.ny * sd.tb.nz &&
-            A.nrows % 2 == 0) {
-            TbGeom g = sd.tb;  // (y-fastest tiles: x-fastest measured +-2 %, profiles/r05_l/)
-            const int tiles = g.tiles_x * g.tiles_y;
-            // z chunks: ~4 workgroups per CU (1024), chunks of >= 16 planes; zm_chunks overrides
-            int zc = options().zm_chunks > 0 ? options().zm_chunks : std::min((1024 + tiles - 1) / tiles, g.nz / 16);
-            zc = std::max(1, std::min(zc, g.nz));
-            g.zlen = (g.nz + zc - 1) / zc;
-            g.zchunks = (g.nz + g.zlen - 1) / g.zlen;
-            const int gr = (tiles * g.zchunks + 7) / 8 * 8;
-            k_sym_zm<OP><<<gr, kZmThreads, 0, s>>>((int)A.nrows, sd.d_tid, sd.d_vtab, sd.d_mtab, sd.vd_n, g, x, b, y,
-                                                   omega);
-            return;
-        }
+        if (launch_sym_zm<OP>(A, x, b, y, omega, s)) return;
     }
     if (sd.vd_n) {  // (the upload builds the dictionary only with two rows per lane)
         const int ch = NU <= 3 ? options().symd_chunks : 1;
@@ -2515,9 +2614,15 @@ void launch_sym_nu(const pamg_mat& A, const double* x, const double* b, double* 
 }
 
 template <int OP>
-void launch_sym(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s) {
+void launch_sym(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s,
+                Cheb ch = Cheb{}) {
     if constexpr (OP == OP_PROLONG) {
         return;  // square operators only (the upload never builds the layout for P)
+    } else if constexpr (OP == OP_CHEB) {
+        // native in k_sym_zm; k_rows_sym / sym2 / symd: the residual into y, then the step over it
+        if (launch_sym_zm<OP_CHEB>(A, x, b, y, omega, s, ch)) return;
+        launch_sym<OP_RESID>(A, x, b, y, 0.0, s);
+        launch_cheb_update(A, x, ch.xold, y, ch.c1, omega, s);
     } else {
         switch (A.sym.nu) {
             case 1: launch_sym_nu<OP, 1>(A, x, b, y, omega, s); break;
@@ -2563,14 +2668,15 @@ void launch_rpat(const pamg_mat& A, const double* x, const double* b, double* y,
 
 template <int OP>
 void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const double* b,
-                    double* y, double omega, hipStream_t s) {
-    if (ts.sym) launch_sym<OP>(A, x, b, y, omega, s);
+                    double* y, double omega, hipStream_t s, Cheb ch = Cheb{}) {
+    if (ts.sym) launch_sym<OP>(A, x, b, y, omega, s, ch);
     if (ts.ell) {
         const EllSet& E = A.ell;
         const int grid = (int)((E.ngroups + 7) / 8 * 8);
         auto go = [&](auto kern) {
             kern<<<grid, kEllGroup, 0, s>>>((int)A.nrows, E.d_gorder, E.d_anc, E.d_smeta, E.d_ci, E.d_vi, E.d_len,
-                                            E.d_gmeta, E.d_otab, E.d_vtab, (int)E.ngroups, x, b, y, omega);
+                                            E.d_gmeta, E.d_otab, E.d_vtab, (int)E.ngroups, x, b, y, omega, ch.c1,
+                                            ch.xold);
         };
         if (E.win) {
             const int win = std::max(E.max_window, 128);
@@ -2578,7 +2684,7 @@ void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const
             k_rows_ellw<OP><<<grid, kEllGroup, lds, s>>>(
                 (int)A.nrows, E.d_gslices, E.d_smeta, E.d_ci, E.d_len, E.d_dpos, E.d_gmeta, E.d_otab, E.d_vtab, E.d_wmeta,
                 E.d_chunks, E.d_lof, win, (reinterpret_cast<uintptr_t>(x) & 15) != 0 ? 1 : 0, (int)E.ngroups, x, b, y,
-                omega);
+                omega, ch.c1, ch.xold);
         } else if (E.d_anc) {
             if (E.paired) go(k_rows_ell<OP, true, true>);
             else go(k_rows_ell<OP, true, false>);
@@ -2587,16 +2693,19 @@ void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const
             else go(k_rows_ell<OP, false, false>);
         }
     }
-    if (ts.pnc) launch_pnc<OP>(A, x, b, y, omega, s);
-    if (ts.rpat) launch_rpat<OP>(A, x, b, y, omega, s);
+    // (pnc and rpat hold prolongations and restrictions: no OP_CHEB — the API refuses it before)
+    if constexpr (OP != OP_CHEB) {
+        if (ts.pnc) launch_pnc<OP>(A, x, b, y, omega, s);
+        if (ts.rpat) launch_rpat<OP>(A, x, b, y, omega, s);
+    }
     if (ts.n_short > 0) {
-        if (ts.tile_nnz == 1024) launch_tile<OP, 1024>(A, ts, x, b, y, omega, s);
-        else if (ts.tile_nnz == 4096) launch_tile<OP, 4096>(A, ts, x, b, y, omega, s);
-        else launch_tile<OP, 2048>(A, ts, x, b, y, omega, s);
+        if (ts.tile_nnz == 1024) launch_tile<OP, 1024>(A, ts, x, b, y, omega, s, ch);
+        else if (ts.tile_nnz == 4096) launch_tile<OP, 4096>(A, ts, x, b, y, omega, s, ch);
+        else launch_tile<OP, 2048>(A, ts, x, b, y, omega, s, ch);
     }
     if (ts.n_long > 0)
         k_rows_long<OP><<<ts.n_long, kBlock, 0, s>>>(ts.d_long, A.d_rowptr, A.d_col, A.d_val, x,
-                                                     b, y, omega);
+                                                     b, y, omega, ch.c1, ch.xold);
 }
 }  // namespace
 
@@ -2657,13 +2766,23 @@ void launch_sym_planes(const pamg_mat& A, int op, int p0, int p1, const double* 
 }
 
 void launch_rows(const pamg_mat& A, const TileSet& ts, int op, const double* x, const double* b,
-                 const double* /*xold*/, double* y, double omega, hipStream_t s) {
+                 const double* xold, double* y, double omega, hipStream_t s, double c1) {
     switch (op) {
         case OP_SPMV: launch_rows_op<OP_SPMV>(A, ts, x, b, y, omega, s); break;
         case OP_RESID: launch_rows_op<OP_RESID>(A, ts, x, b, y, omega, s); break;
         case OP_JACOBI: launch_rows_op<OP_JACOBI>(A, ts, x, b, y, omega, s); break;
+        case OP_CHEB: launch_rows_op<OP_CHEB>(A, ts, x, b, y, omega, s, Cheb{c1, xold}); break;
         default: launch_rows_op<OP_PROLONG>(A, ts, x, b, y, omega, s); break;
     }
+}
+
+void launch_cheb_update(const pamg_mat& A, const double* x, const double* xold, double* y, double c1, double c2,
+                        hipStream_t s) {
+    const SymDia& sd = A.sym;
+    if (A.nrows <= 0) return;
+    const uint32_t in_flag = 2 * sd.nu + 1 <= 7 ? 0x80u : 0x8000u;  // (SymMask<NU>::kIn)
+    k_cheb_update<<<grid_for(A.nrows), kBlock, 0, s>>>(A.nrows, sd.d_mask, sd.mask_bytes, sd.vd_n ? sd.d_tid : nullptr,
+                                                      sd.d_mtab, in_flag, A.d_diag, x, xold, y, c1, c2);
 }
 
 void launch_jacobi_zero(int64_t n, const double* b, const double* diag, double omega, double* y,

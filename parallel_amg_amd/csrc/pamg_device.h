@@ -42,6 +42,9 @@ enum RowOp : int {
     OP_RESID = 1,    // y = b - A x
     OP_JACOBI = 2,   // y = x + (omega (b - A x)) / a_ii
     OP_PROLONG = 3,  // y = y + A x      (x += P e)
+    // (4, 5: the temporally blocked passes of pamg_bench_rowop)
+    OP_CHEB = 6,     // y = x + (c1 (x - xold) + (c2 (b - A x)) / a_ii): Chebyshev step k >= 1 (SPEC §S9);
+                     // c2 travels in the omega argument, a null xold stands for a zero vector
 };
 
 struct TileSet {
@@ -419,8 +422,14 @@ struct pamg_mat {
 namespace pamg {
 
 // kernels.hip launchers (all asynchronous on `s`).
+// (c1 and xold: OP_CHEB only — its c2 is `omega`; square operators only, never the pnc / rpat sets)
 void launch_rows(const pamg_mat& A, const TileSet& ts, int op, const double* x, const double* b,
-                 const double* xold, double* y, double omega, hipStream_t s);
+                 const double* xold, double* y, double omega, hipStream_t s, double c1 = 0.0);
+// y[i] = x[i] + (c1 (x[i] - xold[i]) + (c2 y[i]) / diag[i]) in place, y holding the residual b - A x: the
+// Chebyshev step of the layouts without a native OP_CHEB (k_rows_sym / sym2 / symd), the same seven
+// roundings. Rows outside the symmetric set (a part's boundary rows) keep their y.
+void launch_cheb_update(const pamg_mat& A, const double* x, const double* xold, double* y, double c1, double c2,
+                        hipStream_t s);
 void launch_jacobi_zero(int64_t n, const double* b, const double* diag, double omega, double* y,
                         hipStream_t s);
 void launch_dense_gemv(int64_t n_rows, int64_t n_cols, int64_t row0, const double* ainv_rm,

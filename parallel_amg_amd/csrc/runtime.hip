@@ -11,6 +11,7 @@
 #include <functional>
 #include <iterator>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <cstdio>
@@ -2569,8 +2570,13 @@ int exchange_on(const pamg_plan* plan, double* x, hipStream_t s) {
 }
 
 // y = op(A, x[, b]) with x's ghosts exchanged first; interior rows overlap the exchange.
+// OP_CHEB (SPEC §S9 step k >= 1): omega is c2, xold the own rows of x_{k-1} (null: zeros); y
+// differs from x and xold.
 int apply(pamg_ctx* ctx, const pamg_mat* A, int op, double* x, const double* b, double* y,
-          double omega) {
+          double omega, double c1 = 0.0, const double* xold = nullptr) {
+    if (op != pamg::OP_CHEB) xold = x;
+    else if (A->interior.pnc || A->interior.rpat || (!A->d_diag && A->nrows > 0))
+        return fail(PAMG_E_ARG, "chebyshev: a square operator with a nonzero diagonal is needed");
     hipStream_t s = ctx->s_comp;
     bool comm = A->plan && !A->plan->nbr.empty();
     if (comm && sync_transport(ctx)) {  // debug / in-process transport: exchange first, no overlap
@@ -2583,10 +2589,46 @@ int apply(pamg_ctx* ctx, const pamg_mat* A, int op, double* x, const double* b, 
         CHECK(exchange_on(A->plan, x, ctx->s_comm));
         HIPC(hipEventRecord(ctx->ev_join, ctx->s_comm));
     }
-    pamg::launch_rows(*A, A->interior, op, x, b, x, y, omega, s);
+    pamg::launch_rows(*A, A->interior, op, x, b, xold, y, omega, s, c1);
     if (comm) HIPC(hipStreamWaitEvent(s, ctx->ev_join, 0));
-    pamg::launch_rows(*A, A->boundary, op, x, b, x, y, omega, s);
+    pamg::launch_rows(*A, A->boundary, op, x, b, xold, y, omega, s, c1);
     HIPC(hipGetLastError());
+    return PAMG_OK;
+}
+
+// SPEC §S9 coefficients of a degree-m polynomial over [lmax / ratio, lmax]: fp64, one rounded
+// operation each, in the order the specification fixes (built with -ffp-contract=off)
+constexpr int kChebMaxDeg = 64;
+void cheb_coeffs(double lmax, double ratio, int m, double* c1, double* c2) {
+    const double lmin = lmax / ratio;
+    const double theta = (lmax + lmin) / 2.0, delta = (lmax - lmin) / 2.0, sigma = theta / delta;
+    c1[0] = 0.0;
+    c2[0] = 1.0 / theta;
+    double r = 1.0 / sigma;
+    for (int k = 1; k < m; ++k) {
+        const double rk = 1.0 / (2.0 * sigma - r);
+        c1[k] = rk * r;
+        c2[k] = (2.0 * rk) / delta;
+        r = rk;
+    }
+}
+
+// One Chebyshev polynomial of degree m on level operator A (SPEC §S9). in: x_0, or null for a zero
+// guess (step 0 is then the zero-guess Jacobi form and step 1 passes a null xold). The iterates
+// rotate through ring[0..2] — x_1 into ring[0], x_2 into ring[1], ... — three distinct vectors none
+// of which is `in` or b unless the caller knows `in` dead by then: step k writes ring[k % 3], reads
+// x_k = ring[(k - 1) % 3] and x_{k-1} = ring[(k - 2) % 3] (k = 1: in), so y never aliases x or
+// xold. Returns the vector holding x_m.
+int cheb_poly(pamg_ctx* ctx, const pamg_mat* A, int64_t nown, const double* c1, const double* c2, int m, double* in,
+              const double* b, double* const ring[3], double** out) {
+    hipStream_t s = ctx->s_comp;
+    if (in) CHECK(apply(ctx, A, pamg::OP_JACOBI, in, b, ring[0], c2[0]));
+    else pamg::launch_jacobi_zero(nown, b, A->d_diag, c2[0], ring[0], s);
+    for (int k = 1; k < m; ++k) {
+        const double* xo = k == 1 ? in : ring[(k - 2) % 3];
+        CHECK(apply(ctx, A, pamg::OP_CHEB, ring[(k - 1) % 3], b, ring[k % 3], c2[k], c1[k], xo));
+    }
+    *out = ring[(m - 1) % 3];
     return PAMG_OK;
 }
 
@@ -2727,7 +2769,14 @@ struct pamg_hier {
     int* d_perm = nullptr;
     double *px = nullptr, *pb = nullptr;
     // profiling
-    int nu1 = 1, nu2 = 1;  // V(nu1, nu2) Jacobi sweeps (SPEC §S6)
+    int nu1 = 1, nu2 = 1;  // V(nu1, nu2) Jacobi sweeps (SPEC §S6) / Chebyshev degrees (§S9)
+    // smoother (pamg_hier_set_smoother): with PAMG_SMOOTHER_CHEBYSHEV level l's polynomial runs over
+    // [lmax[l] / ratio, lmax[l]]; c1 / c2: its step coefficients for every degree up to kChebMaxDeg
+    // (the coefficients of degree m are the first m)
+    int smoother = PAMG_SMOOTHER_JACOBI;
+    double cheb_ratio = 4.0;
+    std::vector<double> cheb_lmax;
+    std::vector<std::vector<double>> cheb_c1, cheb_c2;
     bool prof = false;
     std::vector<hipEvent_t> ev;
     std::vector<std::pair<int, int>> ev_tag;  // (level, op) per event pair
@@ -2831,6 +2880,19 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
     // ping-pong between them); the residual goes to the other one; the post-smoothing
     // sweeps ping-pong between x[l] and the spare so that the last one writes x[l]
     std::vector<double*> cur(L, nullptr), spare(L, nullptr);
+    // Chebyshev smoother (SPEC §S9): a polynomial's iterates rotate through three vectors (cheb_poly)
+    // — the level's x, t and r, the input x_0 being free again from step 2 on — so the post-smoothed
+    // iterate of a level >= 1 ends in whichever of them the degrees select (xres, read by the
+    // prolongation above it); on level 0 it must end in the caller's x, which the choice of the
+    // rings arranges (with the spare u0 where the two degrees' remainders mod 3 disagree, need_u0)
+    const bool cheb = H->smoother == PAMG_SMOOTHER_CHEBYSHEV;
+    std::vector<double*> xres(H->x);
+    auto others = [&](int l, const double* not_this, double* out[4]) {  // the level's vectors, x[l] last
+        int n = 0;
+        for (double* v : {H->t[l], H->r[l], l == 0 ? H->u0 : (double*)nullptr, H->x[l]})
+            if (v && v != not_this) out[n++] = v;
+        return n;
+    };
     for (int l = 0; l < L - 1; ++l) {
         const pamg_mat* A = H->A[l];
         double *c = H->t[l], *o = H->r[l];
@@ -2843,12 +2905,33 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
         }
         // level 0, V(1, nu2) from a given guess: the pre-smoothing sweep and the residual in one
         // temporally blocked pass (k_sym_tb, S = 2; both timed as jacobi_pre)
-        const bool fuse = l == 0 && !zero0 && H->nu1 == 1 && pamg::options().jr_fuse && A->interior.sym &&
+        const bool fuse = !cheb && l == 0 && !zero0 && H->nu1 == 1 && pamg::options().jr_fuse && A->interior.sym &&
                           A->sym.tb_ok && !(A->plan && !A->plan->nbr.empty());
         // one part of several: the blocked pass on the slab's inner planes (jr_part)
-        const bool fuse_part = !fuse && l == 0 && !zero0 && H->nu1 == 1 && pamg::options().jr_fuse &&
+        const bool fuse_part = !cheb && !fuse && l == 0 && !zero0 && H->nu1 == 1 && pamg::options().jr_fuse &&
                                A->interior.sym && A->sym.tb_part;
-        if (fuse_part) {
+        if (cheb) {
+            ProfScope p(H, l, 0, s);
+            double* in = l == 0 && !zero0 ? H->x[0] : nullptr;
+            double* ring[3] = {H->t[l], H->r[l], H->x[l]};
+            const int last = (H->nu1 - 1) % 3;
+            if (l == 0) {
+                const bool want_x0 = H->nu2 % 3 == 0;  // the post-smoothing ring ends where it starts
+                if (in) {  // x[0] is x_0: ring[2] or nothing
+                    if (last == 2 && !want_x0) ring[2] = H->u0;
+                } else if (want_x0) {
+                    std::swap(ring[last], ring[2]);
+                } else if (last == 2) {
+                    std::swap(ring[0], ring[2]);
+                }
+            }
+            if (!ring[2]) return fail(PAMG_E_STATE, "vcycle: the Chebyshev cycle lacks its spare level-0 vector");
+            CHECK(cheb_poly(ctx, A, H->nown[l], H->cheb_c1[l].data(), H->cheb_c2[l].data(), H->nu1, in, H->b[l], ring,
+                            &c));
+            double* oth[4];
+            others(l, c, oth);
+            o = oth[0];
+        } else if (fuse_part) {
             ProfScope p(H, l, 0, s);
             CHECK(jr_part(ctx, A, H->x[0], H->b[0], c, o, H->omega[0]));
         } else if (fuse) {
@@ -2897,10 +2980,27 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
     for (int l = L - 2; l >= 0; --l) {
         {
             ProfScope p(H, l, 3, s);
-            CHECK(apply(ctx, H->P[l], pamg::OP_PROLONG, H->x[l + 1], nullptr, cur[l], 0.0));
+            CHECK(apply(ctx, H->P[l], pamg::OP_PROLONG, xres[l + 1], nullptr, cur[l], 0.0));
         }
         if (l == 0 && !seg.post) break;
-        {
+        if (cheb) {
+            ProfScope p(H, l, 4, s);
+            double* oth[4];
+            const int no = others(l, cur[l], oth);
+            double* ring[3] = {oth[0], oth[1], cur[l]};
+            const int last = (H->nu2 - 1) % 3;
+            if (l == 0 && last == 2 && cur[0] != H->x[0]) {
+                if (no < 3) return fail(PAMG_E_STATE, "vcycle: the Chebyshev cycle lacks its spare level-0 vector");
+                ring[2] = H->x[0];  // (oth[0], oth[1]: t, r or u0)
+            } else if (l == 0 && last < 2) {
+                if (cur[0] == H->x[0]) return fail(PAMG_E_STATE, "vcycle: Chebyshev ring order");
+                ring[last] = H->x[0];
+                ring[1 - last] = oth[0];
+            }
+            CHECK(cheb_poly(ctx, H->A[l], H->nown[l], H->cheb_c1[l].data(), H->cheb_c2[l].data(), H->nu2, cur[l],
+                            H->b[l], ring, &xres[l]));
+            if (l == 0 && xres[0] != H->x[0]) return fail(PAMG_E_STATE, "vcycle: Chebyshev ring order");
+        } else {
             ProfScope p(H, l, 4, s);
             double* in = cur[l];
             for (int k = 0; k < H->nu2; ++k) {
@@ -4175,6 +4275,72 @@ int pamg_hier_set_sweeps(pamg_hier* H, int nu1, int nu2) {
     return PAMG_OK;
 }
 
+int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ratio) {
+    if (!H || (kind != PAMG_SMOOTHER_JACOBI && kind != PAMG_SMOOTHER_CHEBYSHEV))
+        return fail(PAMG_E_ARG, "hier_set_smoother: bad hierarchy or smoother kind");
+    const int nl = H->L - 1;
+    std::vector<double> lm;
+    if (kind == PAMG_SMOOTHER_CHEBYSHEV) {
+        if (!(ratio > 1.0) || !std::isfinite(ratio)) return fail(PAMG_E_ARG, "hier_set_smoother: ratio must be > 1");
+        if (nl > 0 && !lmax) return fail(PAMG_E_ARG, "hier_set_smoother: lmax is NULL");
+        for (int l = 0; l < nl; ++l) {
+            if (!(lmax[l] > 0.0) || !std::isfinite(lmax[l]))
+                return fail(PAMG_E_ARG, "hier_set_smoother: lmax[%d] must be > 0", l);
+            lm.push_back(lmax[l]);
+        }
+    }
+    const bool same = kind == H->smoother && (kind == PAMG_SMOOTHER_JACOBI || (lm == H->cheb_lmax && ratio == H->cheb_ratio));
+    if (!same) {
+        (void)hipSetDevice(H->ctx->device);
+        (void)hipStreamSynchronize(H->ctx->s_comp);
+        drop_graph(H);  // the captured cycle has the old smoother
+    }
+    H->smoother = kind;
+    H->cheb_lmax.clear();
+    H->cheb_c1.clear();
+    H->cheb_c2.clear();
+    if (kind == PAMG_SMOOTHER_CHEBYSHEV) {
+        H->cheb_ratio = ratio;
+        H->cheb_lmax = lm;
+        H->cheb_c1.assign(nl, std::vector<double>(kChebMaxDeg));
+        H->cheb_c2.assign(nl, std::vector<double>(kChebMaxDeg));
+        for (int l = 0; l < nl; ++l) cheb_coeffs(lm[l], ratio, kChebMaxDeg, H->cheb_c1[l].data(), H->cheb_c2[l].data());
+    }
+    return PAMG_OK;
+}
+
+int pamg_chebyshev_coeffs(double lmax, double ratio, int degree, double* c1, double* c2) {
+    if (!c1 || !c2 || !(lmax > 0.0) || !(ratio > 1.0) || !std::isfinite(lmax) || !std::isfinite(ratio) || degree < 1 ||
+        degree > kChebMaxDeg)
+        return fail(PAMG_E_ARG, "chebyshev_coeffs: need lmax > 0, ratio > 1, 1 <= degree <= %d", kChebMaxDeg);
+    cheb_coeffs(lmax, ratio, degree, c1, c2);
+    return PAMG_OK;
+}
+
+int pamg_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp1, pamg_vec* tmp2,
+                   double lmax, double ratio, int degree) {
+    if (!ctx || !A || !x || !b || !tmp1 || !tmp2) return fail(PAMG_E_ARG, "chebyshev: NULL");
+    double c1[kChebMaxDeg], c2[kChebMaxDeg];
+    CHECK(pamg_chebyshev_coeffs(lmax, ratio, degree, c1, c2));
+    if (A->nrows != (A->plan ? A->plan->n_own : A->ncols) || A->interior.pnc || A->interior.rpat)
+        return fail(PAMG_E_ARG, "chebyshev: the operator must be square (%lld rows, %lld own columns)",
+                    (long long)A->nrows, (long long)(A->plan ? A->plan->n_own : A->ncols));
+    CHECK(check_vec_for(A, x, "chebyshev"));
+    CHECK(check_vec_for(A, tmp1, "chebyshev"));
+    CHECK(check_vec_for(A, tmp2, "chebyshev"));
+    if (!A->d_diag && A->nrows > 0) return fail(PAMG_E_SETUP, "chebyshev: matrix lacks a nonzero diagonal");
+    if (b->n_own != A->nrows || tmp1 == x || tmp2 == x || tmp1 == tmp2 || b == x || b == tmp1 || b == tmp2)
+        return fail(PAMG_E_ARG, "chebyshev: size mismatch or aliasing");
+    CHECK(set_device(ctx));
+    double* ring[3] = {tmp1->d, tmp2->d, x->d};  // (x is x_0: free again from step 2 on)
+    double* res = nullptr;
+    CHECK(cheb_poly(ctx, A, A->nrows, c1, c2, degree, x->d, b->d, ring, &res));
+    if (res != x->d)
+        HIPC(hipMemcpyAsync(x->d, res, sizeof(double) * x->n_own, hipMemcpyDeviceToDevice, ctx->s_comp));
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
 int pamg_hier_set_perm(pamg_hier* H, int64_t n, const int64_t* perm) {
     if (!H) return fail(PAMG_E_ARG, "hier_set_perm: NULL");
     pamg_ctx* ctx = H->ctx;
@@ -4299,18 +4465,24 @@ static int pipe_enqueue(pamg_hier* H, double* x, const double* b, int seg) {
 static bool pipe_ok(const pamg_hier* H, int ncycles, bool zero0) {
     if (zero0 || ncycles < 2 || H->L < 2 || H->prof || !pamg::options().jr_fuse || H->nu1 != 1 || H->nu2 != 1)
         return false;
+    if (H->smoother != PAMG_SMOOTHER_JACOBI) return false;  // (the chain kernels are Jacobi sweeps)
     const pamg_mat* A = H->A[0];
     if (!A->interior.sym) return false;
     return (H->ctx->nranks == 1 && A->sym.tb_ok && !(A->plan && !A->plan->nbr.empty())) || A->sym.tb_part;
 }
 
+// the spare level-0 vector (the pipeline's second iterate; the Chebyshev cycle's fourth ring vector)
+static int ensure_u0(pamg_hier* H) {
+    if (H->u0) return PAMG_OK;
+    const int64_t n = H->nown[0] + (H->A[0]->plan ? H->A[0]->plan->n_ghost : 0) + kVecPad;
+    CHECK(dalloc(&H->u0, n));
+    CHECK(dzero(H->ctx, H->u0, sizeof(double) * n));
+    return PAMG_OK;
+}
+
 static int vcycle_pipe(pamg_hier* H, double* x, const double* b, int ncycles) {
     pamg_ctx* ctx = H->ctx;
-    if (!H->u0) {
-        const int64_t n = H->nown[0] + (H->A[0]->plan ? H->A[0]->plan->n_ghost : 0) + kVecPad;
-        CHECK(dalloc(&H->u0, n));
-        CHECK(dzero(H->ctx, H->u0, sizeof(double) * n));
-    }
+    CHECK(ensure_u0(H));
     const int K = ncycles;
     auto seg_of = [K](int k) { return k == 0 ? 0 : k < K ? (k % 2 == 1 ? 1 : 2) : ((K - 1) % 2 == 1 ? 4 : 3); };
     if (H->use_graph && (!H->g_head || H->gp_x != x || H->gp_b != b)) {
@@ -4357,6 +4529,10 @@ static int vcycle_raw(pamg_hier* H, double* x, const double* b, int ncycles, boo
     if (zero0 && ncycles != 1) return fail(PAMG_E_ARG, "vcycle: zero initial guess applies to one cycle");
     // stationary runs of >= 2 cycles: the cross-cycle pipeline (same operations, same bits)
     if (pipe_ok(H, ncycles, zero0)) return vcycle_pipe(H, x, b, ncycles);
+    // Chebyshev from a given guess: level 0's rings need a fourth vector where exactly one of the two
+    // degrees is a multiple of 3 (vcycle_enqueue); allocated before any capture
+    if (H->smoother == PAMG_SMOOTHER_CHEBYSHEV && H->L > 1 && !zero0 && (H->nu1 % 3 == 0) != (H->nu2 % 3 == 0))
+        CHECK(ensure_u0(H));
     if (H->use_graph && !H->prof && (!H->gexec || H->g_x != x || H->g_b != b || H->g_zero0 != zero0)) {
         // Capture one cycle (RCCL exchanges included on several parts: RCCL records its
         // send/recv/all-gather as graph nodes). If capture fails, fall back to eager launches
@@ -4625,11 +4801,7 @@ int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps
     pamg_ctx* ctx = H->ctx;
     CHECK(check_vec_for(H->A[0], x, "hier_bench_chain"));
     CHECK(set_device(ctx));
-    if (!H->u0) {
-        const int64_t n = H->nown[0] + (H->A[0]->plan ? H->A[0]->plan->n_ghost : 0) + kVecPad;
-        CHECK(dalloc(&H->u0, n));
-        CHECK(dzero(H->ctx, H->u0, sizeof(double) * n));
-    }
+    CHECK(ensure_u0(H));
     hipEvent_t e0, e1;
     HIPC(hipEventCreate(&e0));
     HIPC(hipEventCreate(&e1));
@@ -4649,11 +4821,43 @@ int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps
 
 int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, const pamg_vec* b,
                      pamg_vec* y, double omega, int reps, double* avg_ms) {
-    if (!ctx || !A || !x || !y || reps < 1 || !avg_ms || op < 0 || op > 5)
+    if (!ctx || !A || !x || !y || reps < 1 || !avg_ms || op < 0 || op > 6)
         return fail(PAMG_E_ARG, "bench_rowop: bad args");
     if ((op == pamg::OP_RESID || op == pamg::OP_JACOBI || op >= 4) && !b) return fail(PAMG_E_ARG, "bench_rowop: b needed");
     if ((op == pamg::OP_JACOBI || op >= 4) && !A->d_diag)
         return fail(PAMG_E_SETUP, "bench_rowop: jacobi needs a square matrix");
+    if (op == pamg::OP_CHEB) {  // one Chebyshev step k >= 1: c1 = c2 = omega, x_{k-1} a zeroed vector of the call's
+        if (A->interior.pnc || A->interior.rpat) return fail(PAMG_E_ARG, "bench_rowop: op 6 needs a square operator");
+        if (x == y || b == y) return fail(PAMG_E_ARG, "bench_rowop: y must differ from x and b");
+        CHECK(check_vec_for(A, x, "bench_rowop"));
+        if (b->n_own != A->nrows || y->n_own != A->nrows) return fail(PAMG_E_ARG, "bench_rowop: size mismatch");
+        CHECK(set_device(ctx));
+        double* xo = nullptr;
+        CHECK(dalloc(&xo, A->nrows + kVecPad));
+        int rc = dzero(ctx, xo, sizeof(double) * (size_t)(A->nrows + kVecPad));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        hipStream_t s = ctx->s_comp;
+        auto once = [&]() {
+            pamg::launch_rows(*A, A->interior, op, x->d, b->d, xo, y->d, omega, s, omega);
+            pamg::launch_rows(*A, A->boundary, op, x->d, b->d, xo, y->d, omega, s, omega);
+        };
+        float ms = 0.f;
+        if (rc == PAMG_OK && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = PAMG_E_HIP;
+        if (rc == PAMG_OK) {
+            once();
+            (void)hipEventRecord(e0, s);
+            for (int k = 0; k < reps; ++k) once();
+            (void)hipEventRecord(e1, s);
+            if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess ||
+                hipGetLastError() != hipSuccess)
+                rc = fail(PAMG_E_HIP, "bench_rowop: op 6 failed");
+        }
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        dfree(xo);
+        *avg_ms = ms / reps;
+        return rc;
+    }
     if (op >= 4 && !(A->interior.sym && (A->sym.tb_ok || A->sym.tb_part)))
         return fail(PAMG_E_STATE, "bench_rowop: op %d needs the temporally blocked layout (pamg_mat_layout bit 5)", op);
     if (x == y) return fail(PAMG_E_ARG, "bench_rowop: x and y must differ");

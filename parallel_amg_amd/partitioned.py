@@ -396,6 +396,24 @@ def jacobi(x: PVector, A: PSparseMatrix, b: PVector, tmp: PVector, omega: float,
     return x
 
 
+def chebyshev_coeffs(lmax: float, ratio: float = 4.0, degree: int = 2):
+    """The step coefficients (c1, c2) of the degree-``degree`` Chebyshev smoother over
+    [lmax / ratio, lmax] (SPEC §S9), as two float64 arrays of length ``degree``; c1[0] is 0."""
+    n = max(int(degree), 1)
+    c1, c2 = np.zeros(n), np.zeros(n)
+    call("pamg_chebyshev_coeffs", float(lmax), float(ratio), int(degree), ptr(c1), ptr(c2))
+    return c1, c2
+
+
+def chebyshev(x: PVector, A: PSparseMatrix, b: PVector, tmp1: PVector, tmp2: PVector, lmax: float,
+              ratio: float = 4.0, degree: int = 2) -> PVector:
+    """One Chebyshev polynomial smoother of the given degree on x (SPEC §S9; result in x). tmp1 and
+    tmp2 are work vectors shaped like x (``A.new_input_vector()``)."""
+    call("pamg_chebyshev", A.ctx.handle, A.handle, x.handle, b.handle, tmp1.handle, tmp2.handle, float(lmax),
+         float(ratio), int(degree))
+    return x
+
+
 def jacobi_residual(t: PVector, r: PVector, A: PSparseMatrix, x: PVector, b: PVector, omega: float) -> bool:
     """t = x + omega D^-1 (b - A x); r = b - A t. Returns whether the fused pass ran."""
     f = C.c_int(0)

@@ -115,6 +115,7 @@ class AMGSolver:
         call("pamg_hier_create", ctx.handle, L, arrA, arrP, arrR, ptr(om), H.n_coarse,
              ptr(self._ainv), int(rep), ptr(roffs) if roffs is not None else None, C.byref(h))
         self._h = h
+        self.smoother = "jacobi"
         if self.perm[0] is not None:
             p0 = np.ascontiguousarray(self.perm[0], np.int64)
             call("pamg_hier_set_perm", h, len(p0), ptr(p0))
@@ -156,6 +157,17 @@ class AMGSolver:
     def set_sweeps(self, nu1: int, nu2: int):
         """V(nu1, nu2) weighted-Jacobi sweeps (SPEC §S6; default V(1, 1))."""
         call("pamg_hier_set_sweeps", self._h, int(nu1), int(nu2))
+
+    def set_smoother(self, kind: str = "jacobi", ratio: float = 4.0):
+        """The V-cycle's smoother: "jacobi" (default) or "chebyshev" — one polynomial of degree nu1
+        before and nu2 after the coarse correction (``set_sweeps`` gives the degrees), level l over
+        [rho_l / ratio, rho_l] with the setup's bound rho_l (``LevelPart.rho``; SPEC §S9)."""
+        kinds = {"jacobi": 0, "chebyshev": 1}
+        if kind not in kinds:
+            raise ValueError(f"unknown smoother {kind!r} (jacobi | chebyshev)")
+        lmax = np.asarray([self._H.levels[l][self.part].rho for l in range(self.L - 1)], np.float64)
+        call("pamg_hier_set_smoother", self._h, kinds[kind], ptr(lmax) if kinds[kind] else None, float(ratio))
+        self.smoother = kind
 
     def graph_state(self) -> dict:
         e, c, f = C.c_int(), C.c_int(), C.c_int()

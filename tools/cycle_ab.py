@@ -5,6 +5,12 @@ of --steps pipelined V-cycles, synchronised on both sides; the graphs are re-cap
 switch) and checked for the same bits of x.
 
     python tools/cycle_ab.py --ab chain_store_x=1,0 --rounds 3 > ab.jsonl
+
+--pcg compares smoothers instead, on the same upload: each variant — j or c (Jacobi, Chebyshev with
+--ratio) followed by the two sweep counts / degrees — solves A x = b by PCG to --rtol once to warm up
+(and capture) and --rounds times timed; one JSON line per solve with its time and iteration count.
+
+    python tools/cycle_ab.py --pcg j11,j22,j33,c22,c33 --rounds 3 > pcg.jsonl
 """
 from __future__ import annotations
 
@@ -34,12 +40,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--kind", default="poisson3d")
-    ap.add_argument("--ab", required=True, help="KEY=a,b")
+    ap.add_argument("--ab", default=None, help="KEY=a,b")
+    ap.add_argument("--pcg", default=None, help="smoother variants, e.g. j11,j22,c22")
+    ap.add_argument("--ratio", type=float, default=4.0)
+    ap.add_argument("--rtol", type=float, default=1e-8)
+    ap.add_argument("--maxit", type=int, default=100)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
-    key, vals = a.ab.split("=")
-    va, vb = (int(v) for v in vals.split(","))
+    if (a.ab is None) == (a.pcg is None):
+        ap.error("one of --ab and --pcg")
     t0 = time.time()
     ctx = Context(0)
     be = pa.SequentialBackend(1)
@@ -51,6 +61,22 @@ def main():
     b = PVector(ctx, Af.nrows)
     mul(b, Af, PVector(ctx, Af.n_own_cols, Af.n_ghost, xs[0]))
     print(f"# setup + upload {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
+    if a.pcg:
+        for var in a.pcg.split(","):
+            S.set_smoother({"j": "jacobi", "c": "chebyshev"}[var[0]], ratio=a.ratio)
+            S.set_sweeps(int(var[1]), int(var[2]))
+            for r in range(-1, a.rounds):  # (-1: warm-up and graph capture)
+                x = S.new_vector()
+                ctx.sync()
+                ts = time.perf_counter()
+                its, hist = S.pcg(x, b, a.rtol, a.maxit)
+                dt = time.perf_counter() - ts
+                if r >= 0:
+                    print(json.dumps({"kind": a.kind, "n": a.n, "variant": var, "round": r, "iterations": its,
+                                      "ms": round(dt * 1e3, 3), "rel_residual": float(hist[-1] / hist[0])}), flush=True)
+        return
+    key, vals = a.ab.split("=")
+    va, vb = (int(v) for v in vals.split(","))
     ref = None
     for r in range(a.rounds):
         for v in (va, vb):

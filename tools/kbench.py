@@ -29,7 +29,8 @@ from parallel_amg_amd._lib import call, layout_of  # noqa: E402
 from parallel_amg_amd.partitioned import Context, PSparseMatrix, PVector  # noqa: E402
 from parallel_amg_amd.solver import AMGSolver  # noqa: E402
 
-OPNAME = {0: "spmv", 1: "residual", 2: "jacobi", 3: "prolong", 4: "jacobi_residual_tb", 5: "chain3_tb"}
+OPNAME = {0: "spmv", 1: "residual", 2: "jacobi", 3: "prolong", 4: "jacobi_residual_tb", 5: "chain3_tb",
+          6: "cheb_step"}  # one Chebyshev step k >= 1 (SPEC §S9): b and x_{k-1} beside x
 
 
 def set_opts(**kw):
@@ -44,7 +45,7 @@ def bench(ctx, M, op, reps):
     ms = C.c_double()
     call("pamg_bench_rowop", ctx.handle, M.handle, op, x.handle, b.handle, y.handle, 0.6, reps,
          C.byref(ms))
-    extra = {0: 0, 1: 1, 2: 1, 3: 1, 4: 2, 5: 3}[op]  # fused: b + the other outputs, matrix once
+    extra = {0: 0, 1: 1, 2: 1, 3: 1, 4: 2, 5: 3, 6: 2}[op]  # fused: b + the other outputs, matrix once; 6: b, x_{k-1}
     return ms.value, AMGSolver.csr_bytes(M, extra), AMGSolver.rowsum_bytes(M, extra)
 
 
@@ -112,9 +113,9 @@ def main():
                 continue
             D = PSparseMatrix(ctx, M, plan)
             for op in ops:
-                if op in (2, 4, 5) and not name.startswith("A"):
+                if op in (2, 4, 5, 6) and not name.startswith("A"):
                     continue
-                if op >= 4 and not layout_of(D).get("jr_fused"):
+                if op in (4, 5) and not layout_of(D).get("jr_fused"):
                     continue
                 if op == 3 and not name.startswith("P"):
                     continue
