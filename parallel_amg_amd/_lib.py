@@ -6,6 +6,7 @@ entry point raises, so a test can never pass on a silent CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -187,6 +188,18 @@ def call(name, *args):
         msg = L.pamg_last_error().decode(errors="replace")
         raise PamgError(rc, name, msg)
     return rc
+
+
+@contextlib.contextmanager
+def option(key: str, value: int):
+    """Set one pamg_set_option key for the duration of a ``with`` block, then put the old value back."""
+    old = C.c_int64()
+    call("pamg_get_option", key.encode(), C.byref(old))
+    call("pamg_set_option", key.encode(), int(value))
+    try:
+        yield
+    finally:
+        call("pamg_set_option", key.encode(), old.value)
 
 
 def layout_of(M, part_set: int = 0) -> dict:

@@ -2221,7 +2221,91 @@ int build_rpat(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* va
     return PAMG_OK;
 }
 
-void free_rpat(pamg::RpatSet& R) {
+// ---- the layout families' interfaces
+// What pamg_mat_upload hands to each family in turn. A->ctx, the shapes, nnz and the plan are
+// set; `inner` lists the interior rows no family has taken yet (ascending).
+struct Upload {
+    pamg_mat* A;
+    const PtrVec& rp;                // row pointers, base 0
+    const IdxVec& ci;                // columns, base 0 (own columns first, then ghosts)
+    const double* val;
+    int64_t n_own_cols;
+    bool has_all_diag;               // square with a nonzero diagonal in every row
+    std::vector<int>& inner;
+    const std::vector<int>& bnd;     // the rows with ghost columns (always tiles)
+    const std::function<int64_t()>& band;  // the banded tile order's row distance, computed on first use
+    UploadTrace& tr;
+};
+// Every family provides four functions. X_try holds the family's eligibility rule and its
+// builder: where it takes the rows it sets its TileSet flag on A->interior and clears
+// u.inner; where it declines it leaves both; PAMG_OK either way, an error only for a failed
+// allocation or copy. X_free releases the family's device arrays and resets its struct. X_bytes
+// is its share of pamg_mat_stream_bytes (0 where it holds no rows). X_report writes its slots and
+// bits of pamg_mat_layout's out[10] for tile set t (nothing where t is not its).
+int sym_try(Upload& u) {
+    pamg_mat* A = u.A;
+    if (pamg::options().sym_dia && u.n_own_cols == A->nrows && u.has_all_diag && !u.inner.empty())
+        CHECK(build_sym_dia(A, u.rp, u.ci, u.val, u.inner, u.band));
+    if (A->interior.sym) u.inner.clear();  // the interior rows run in k_rows_sym, not in tiles
+    u.tr.mark("sym dia");
+    return PAMG_OK;
+}
+
+void sym_free(pamg::SymDia& S) {
+    dfree(S.d_mask);
+    dfree(S.d_diag);
+    dfree(S.d_upper);
+    dfree(S.d_tid);
+    dfree(S.d_vtab);
+    dfree(S.d_mtab);
+    S = pamg::SymDia{};
+}
+
+// 8/16-bit mask, diagonal and nu upper values per row (the mirrored lower values are the same
+// lines, re-read from cache)
+int64_t sym_bytes(const pamg_mat* A) {
+    if (!A->interior.sym) return 0;
+    const int64_t nrows = A->nrows;
+    return A->sym.vd_n ? nrows + (int64_t)A->sym.vd_n * (8 * (A->sym.nu + 1) + 4)
+                       : nrows * (A->sym.mask_bytes + 8 + 8 * (int64_t)A->sym.nu);
+}
+
+void sym_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
+    if (!t.sym) return;
+    out[4] = A->sym.nu;  // upper classes, k_rows_sym's grid
+    out[8] = A->sym.nbands * 8 * A->sym.eighth;
+    out[9] |= 8 | (A->sym.rpl == 2 ? 16 : 0) | (A->sym.tb_ok || A->sym.tb_part ? 32 : 0) | (A->sym.vd_n ? 128 : 0);
+}
+
+// restrictions whose rows repeat few patterns (an aggregate shape each); several parts: the interior
+// rows, when they are >= 3/4 of the operator — a 512^3 z-slab part's level 1
+int rpat_try(Upload& u) {
+    pamg_mat* A = u.A;
+    const int64_t nrows = A->nrows;
+    if (pamg::options().rpat && !A->interior.sym && u.n_own_cols > nrows && nrows > 0 &&
+        (int64_t)u.inner.size() * 4 >= (int64_t)nrows * 3) {
+        CHECK(build_rpat(A, u.rp, u.ci, u.val, u.inner));
+        if (A->interior.rpat) u.inner.clear();  // the rows run in k_rows_rpat, not in tiles
+        u.tr.mark("rpat");
+    }
+    return PAMG_OK;
+}
+
+// the first column and the pattern id per row, the tables
+int64_t rpat_bytes(const pamg_mat* A) {
+    if (!A->interior.rpat) return 0;
+    return 5 * A->nrows + 8 * A->rpat.npat + 4 * A->rpat.nent + 8 * A->rpat.nval;
+}
+
+void rpat_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
+    if (!t.rpat) return;
+    out[3] = A->rpat.nval;  // the pattern and value tables, k_rows_rpat's grid
+    out[4] = A->rpat.npat;
+    out[8] = (int)A->rpat.ngroups;
+    out[9] |= 2048;
+}
+
+void rpat_free(pamg::RpatSet& R) {
     dfree(R.d_anc);
     dfree(R.d_pid);
     dfree(R.d_pmeta);
@@ -2231,17 +2315,58 @@ void free_rpat(pamg::RpatSet& R) {
     R = pamg::RpatSet{};
 }
 
-void free_pnc(pamg::PncSet& P) {
-    dfree(P.d_anc);
-    dfree(P.d_rec);
-    dfree(P.d_cid);
-    dfree(P.d_pvals);
-    dfree(P.d_ptab);
-    dfree(P.d_vtab);
-    P = pamg::PncSet{};
+// square operators (offsets from the row) and restrictions (fewer rows than columns; offsets from
+// each row's first column); several parts: the interior rows, when they are >= 3/4 of the operator
+int ell_try(Upload& u) {
+    pamg_mat* A = u.A;
+    const int64_t nrows = A->nrows, n_own_cols = u.n_own_cols;
+    if (pamg::options().ell && !A->interior.sym && !A->interior.rpat && n_own_cols >= nrows && nrows > 0 &&
+        (int64_t)u.inner.size() * 4 >= (int64_t)nrows * 3 && nrows >= pamg::options().ell_min_rows &&
+        (n_own_cols == nrows || pamg::options().ell_restrict)) {
+        CHECK(build_ell(A, u.rp, u.ci, u.val, n_own_cols != nrows, u.inner));
+        if (A->interior.ell) u.inner.clear();  // the rows run in k_rows_ell, not in tiles
+        u.tr.mark("ell");
+    }
+    return PAMG_OK;
 }
 
-void free_ell(pamg::EllSet& E) {
+// two index bytes per padded nonzero, a length byte per row, the slice and group descriptors and
+// the group tables
+int64_t ell_bytes(const pamg_mat* A) {
+    if (!A->interior.ell) return 0;
+    const int64_t nrows = A->nrows;
+    return (A->ell.paired ? 4 : 8) * A->ell.words + nrows + 8 * A->ell.nslices + 16 * A->ell.ngroups + 4 * A->ell.otab_n +
+           8 * A->ell.vtab_n + (A->ell.d_anc ? 4 * nrows : 0) +
+           (A->ell.win ? 32 * A->ell.ngroups + 8 * A->ell.nchunks + 2 * A->ell.lof_n + nrows : 0);
+}
+
+void ell_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
+    if (!t.ell) return;
+    out[8] = (int)A->ell.ngroups;  // k_rows_ell's grid
+    out[9] |= 512 | (A->ell.paired ? 8192 : 0);
+}
+
+void ell_window(const pamg_mat* A, int out[16]) {
+    const pamg::EllSet& E = A->ell;
+    const bool w = A->interior.ell && E.win;
+    out[0] = w ? 1 : 0;
+    out[1] = w ? E.win_groups : 0;
+    out[2] = w ? E.gather_groups : 0;
+    out[3] = w ? E.max_window : 0;
+    out[4] = w ? E.noncontig_groups : 0;
+    out[5] = w ? E.max_pairs : 0;
+    out[6] = w ? E.max_chunks : 0;
+    out[7] = w ? (int)E.ngroups : 0;
+    out[8] = w ? E.mean_window : 0;
+    out[9] = w ? E.p95_window : 0;
+    out[10] = w ? E.mean_runs : 0;
+    out[11] = w ? E.max_runs : 0;
+    out[12] = w ? E.mean_pairs : 0;
+    out[13] = w ? E.full_groups : 0;
+    out[14] = out[15] = 0;
+}
+
+void ell_free(pamg::EllSet& E) {
     dfree(E.d_gorder);
     dfree(E.d_smeta);
     dfree(E.d_ci);
@@ -2259,7 +2384,137 @@ void free_ell(pamg::EllSet& E) {
     E = pamg::EllSet{};
 }
 
-void free_tiles(pamg::TileSet& ts) {
+// a prolongation over a 7-point grid uploaded earlier on this context
+int pnc_try(Upload& u) {
+    pamg_mat* A = u.A;
+    const int64_t nrows = A->nrows;
+    if (pamg::options().pnc && u.n_own_cols < nrows && (int64_t)u.inner.size() * 4 >= (int64_t)nrows * 3) {
+        // (every registered grid of this row count, the latest first: grids of one size but other
+        // shapes may be registered too, and the neighbour check decides)
+        const auto grids = grids_of(A->ctx);
+        for (auto g = grids.rbegin(); g != grids.rend() && !A->interior.pnc; ++g)
+            if ((*g)[0] == nrows) CHECK(build_pnc(A, u.rp, u.ci, u.val, *g, u.inner));
+        if (A->interior.pnc) u.inner.clear();  // the rows run in k_rows_pnc, not in tiles
+        u.tr.mark("pnc");
+    }
+    return PAMG_OK;
+}
+
+// the anchor and the record per row, the two tables
+int64_t pnc_bytes(const pamg_mat* A) {
+    if (!A->interior.pnc) return 0;
+    return (A->pnc.d_cid ? 6 : 12) * A->nrows + (A->pnc.d_cid ? 12 : 4) * A->pnc.npat + 8 * A->pnc.nval;
+}
+
+void pnc_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
+    if (!t.pnc) return;
+    out[3] = A->pnc.nval;  // the pattern and value tables, k_rows_pnc's grid
+    out[4] = A->pnc.npat;
+    out[8] = A->pnc.grid;
+    out[9] |= 1024 | (A->pnc.d_cid ? 4096 : 0);
+}
+
+void pnc_free(pamg::PncSet& P) {
+    dfree(P.d_anc);
+    dfree(P.d_rec);
+    dfree(P.d_cid);
+    dfree(P.d_pvals);
+    dfree(P.d_ptab);
+    dfree(P.d_vtab);
+    P = pamg::PncSet{};
+}
+
+int tiles_try(Upload& u) {
+    pamg_mat* A = u.A;
+    pamg_ctx* ctx = A->ctx;
+    const PtrVec& rp = u.rp;
+    const IdxVec& ci = u.ci;
+    const int64_t nrows = A->nrows, nnz = A->nnz, n_own_cols = u.n_own_cols;
+    std::vector<uint16_t> lo;
+    std::vector<uint8_t> hi, vidx;
+    {
+        std::vector<int4> t_in, t_bd;
+        const bool square = n_own_cols == nrows;
+        const bool tall = n_own_cols < nrows;  // a prolongation's shape
+        const int64_t tb = u.inner.empty() && u.bnd.empty() ? 0 : u.band();
+        CHECK(build_tiles(rp, u.inner, square, &A->interior, tb, ci, &lo, &hi, u.val, &vidx, &t_in, tall));
+        CHECK(build_tiles(rp, u.bnd, square, &A->boundary, tb, ci, &lo, &hi, u.val, &vidx, &t_bd, tall));
+        u.tr.mark("tiles");
+        std::vector<uint8_t> idx8;
+        CHECK(build_col_dicts(A, rp, ci, t_in, t_bd, &idx8));
+        u.tr.mark("col dicts");
+        CHECK(build_tile_major(A, n_own_cols, rp, ci, u.val, t_in, t_bd, lo, hi, idx8));
+        u.tr.mark("tile-major");
+    }
+    if (A->interior.rl8 || A->boundary.rl8) {
+        std::vector<uint8_t> rl(nrows + kVecPad, 0);
+        par_for(nrows, [&](int64_t a, int64_t b) {
+            for (int64_t i = a; i < b; ++i) rl[i] = (uint8_t)std::min<int64_t>(255, rp[i + 1] - rp[i]);
+        });
+        CHECK(dalloc(&A->d_rlen, nrows + kVecPad));
+        CHECK(h2d(ctx, A->d_rlen, rl.data(), rl.size()));
+    }
+    if (!vidx.empty()) {
+        CHECK(dalloc(&A->d_vidx, (int64_t)vidx.size()));
+        CHECK(h2d(ctx, A->d_vidx, vidx.data(), vidx.size()));
+    }
+    if (!lo.empty()) {  // padded like d_col
+        lo.resize(nnz + kVecPad, 0);
+        hi.resize(nnz + kVecPad, 0);
+        CHECK(dalloc(&A->d_clo, nnz + kVecPad));
+        CHECK(dalloc(&A->d_chi, nnz + kVecPad));
+        CHECK(h2d(ctx, A->d_clo, lo.data(), sizeof(uint16_t) * lo.size()));
+        CHECK(h2d(ctx, A->d_chi, hi.data(), sizeof(uint8_t) * hi.size()));
+    }
+    u.tr.mark("rest");  // (before the index streams above are freed, as the trace always timed it)
+    return PAMG_OK;
+}
+
+// the bytes one apply streams, per tile set: long rows (row pointer, 12 B/nonzero, list
+// entry) + short tiles in their layout — row bounds (1 B/row with 8-bit lengths, else 4-B
+// row pointers), columns (4 B; 3 B 24-bit; cd/8 B with a dictionary + its 4-B offsets),
+// values (8 B; or a 4-bit index + the tile's 128-B table), 16-B descriptors (+ a 4-B
+// column base with 24-bit columns); a tile-major set streams whole padded slots
+// (tile_nnz values and column entries, tm_rs row lengths per tile).
+int64_t tiles_bytes(const pamg_mat* A) {
+    int64_t sum = 0;
+    for (const pamg::TileSet* t : {&A->interior, &A->boundary}) {
+        if (t->sym || t->ell || t->pnc || t->rpat) continue;  // counted by their families
+        const int64_t ns = t->n_short, nz = t->nnz_short;
+        int64_t b = 8 * (int64_t)t->n_long + 12 * t->nnz_long;
+        const bool base = t->c24 && !t->cd;
+        if (t->tm) {  // whole padded slots: tile_nnz values + column entries + tm_rs lengths
+            const int64_t tn = t->tile_nnz;
+            const int64_t rowb = t->tm_rs;
+            const int64_t valb = t->tm_vt ? tn + 8 * (int64_t)t->tm_vt : 8 * tn;  // 8-bit indices + table
+            b += ns * (rowb * (t->anc ? 5 : 1) + valb + (t->cd ? t->cd * tn / 8 : 3 * tn) + 16 + (base ? 4 : 0)) +
+                 (t->cd ? 4 * t->ctab_n * (t->pt ? ns : 1) : 0);
+        } else {
+            b += (t->rl8 ? 1 : 4) * t->rows_short;
+            b += t->cd ? (t->cd * nz + 7) / 8 + 4 * t->ctab_n * (t->pt ? ns : 1) : (t->c24 ? 3 : 4) * nz;
+            if (t->pt && t->anc) b += 2 * t->rows_short + 4 * ns;  // 16-bit anchors + tile bases
+            b += t->vd ? nz / 2 + 128 * ns : 8 * nz;
+            b += (16 + (base ? 4 : 0)) * ns;
+        }
+        sum += b;
+    }
+    return sum;
+}
+
+void tiles_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
+    out[0] = t.c24;
+    out[1] = t.vd;
+    out[2] = t.rl8;
+    out[3] = t.cd;
+    out[4] = t.ctab_n;
+    out[5] = t.tm;
+    out[6] = t.tm_rs;
+    out[7] = t.tile_nnz;
+    out[8] = t.n_short;
+    out[9] = (t.anc ? 1 : 0) | (t.pt ? 2 : 0) | (t.xs ? 4 : 0) | (t.tm && t.tm_vt ? 64 : 0);
+}
+
+void tiles_free(pamg::TileSet& ts) {
     dfree(ts.d_short);
     dfree(ts.d_long);
     dfree(ts.d_base);
@@ -2569,6 +2824,36 @@ int exchange_on(const pamg_plan* plan, double* x, hipStream_t s) {
     return PAMG_OK;
 }
 
+// The exchange of x on the comm stream, behind everything already enqueued on the compute
+// stream; `done` is recorded after it (the compute stream, or the caller, waits on that).
+int exchange_fork(pamg_ctx* ctx, const pamg_plan* plan, double* x, hipEvent_t done) {
+    HIPC(hipEventRecord(ctx->ev_fork, ctx->s_comp));
+    HIPC(hipStreamWaitEvent(ctx->s_comm, ctx->ev_fork, 0));
+    CHECK(exchange_on(plan, x, ctx->s_comm));
+    HIPC(hipEventRecord(done, ctx->s_comm));
+    return PAMG_OK;
+}
+
+// One operation on the compute stream whose input v needs its ghosts: `overlapped()` enqueues the
+// work that reads own entries only, `after()` the work that reads ghost slots. With RCCL the
+// exchange runs on the comm stream beside `overlapped` and `after` waits for it; a synchronous
+// transport exchanges first (nothing to overlap). plan null or without neighbours: no exchange.
+template <class F, class G>
+int overlap_exchange(pamg_ctx* ctx, const pamg_plan* plan, double* v, F&& overlapped, G&& after) {
+    hipStream_t s = ctx->s_comp;
+    bool comm = plan && !plan->nbr.empty();
+    if (comm && sync_transport(ctx)) {  // debug / in-process transport: exchange first, no overlap
+        CHECK(exchange_on(plan, v, s));
+        comm = false;
+    }
+    if (comm) CHECK(exchange_fork(ctx, plan, v, ctx->ev_join));
+    overlapped();
+    if (comm) HIPC(hipStreamWaitEvent(s, ctx->ev_join, 0));
+    after();
+    HIPC(hipGetLastError());
+    return PAMG_OK;
+}
+
 // y = op(A, x[, b]) with x's ghosts exchanged first; interior rows overlap the exchange.
 // OP_CHEB (SPEC §S9 step k >= 1): omega is c2, xold the own rows of x_{k-1} (null: zeros); y
 // differs from x and xold.
@@ -2578,22 +2863,9 @@ int apply(pamg_ctx* ctx, const pamg_mat* A, int op, double* x, const double* b, 
     else if (A->interior.pnc || A->interior.rpat || (!A->d_diag && A->nrows > 0))
         return fail(PAMG_E_ARG, "chebyshev: a square operator with a nonzero diagonal is needed");
     hipStream_t s = ctx->s_comp;
-    bool comm = A->plan && !A->plan->nbr.empty();
-    if (comm && sync_transport(ctx)) {  // debug / in-process transport: exchange first, no overlap
-        CHECK(exchange_on(A->plan, x, s));
-        comm = false;
-    }
-    if (comm) {
-        HIPC(hipEventRecord(ctx->ev_fork, s));
-        HIPC(hipStreamWaitEvent(ctx->s_comm, ctx->ev_fork, 0));
-        CHECK(exchange_on(A->plan, x, ctx->s_comm));
-        HIPC(hipEventRecord(ctx->ev_join, ctx->s_comm));
-    }
-    pamg::launch_rows(*A, A->interior, op, x, b, xold, y, omega, s, c1);
-    if (comm) HIPC(hipStreamWaitEvent(s, ctx->ev_join, 0));
-    pamg::launch_rows(*A, A->boundary, op, x, b, xold, y, omega, s, c1);
-    HIPC(hipGetLastError());
-    return PAMG_OK;
+    return overlap_exchange(
+        ctx, A->plan, x, [&]() { pamg::launch_rows(*A, A->interior, op, x, b, xold, y, omega, s, c1); },
+        [&]() { pamg::launch_rows(*A, A->boundary, op, x, b, xold, y, omega, s, c1); });
 }
 
 // SPEC §S9 coefficients of a degree-m polynomial over [lmax / ratio, lmax]: fp64, one rounded
@@ -2648,24 +2920,6 @@ int sweeps_part(pamg_ctx* ctx, const pamg_mat* A, int S, const double* in0, doub
     const pamg::SymDia& sd = A->sym;
     const int nz = sd.tb.nz;
     const int zlo = sd.part_lo == 0 ? 0 : sd.part_lo + S - 1, zhi = sd.part_hi == nz ? nz : sd.part_hi - (S - 1);
-    auto stage = [&](double* v, auto&& overlapped, auto&& after) -> int {
-        bool comm = exch && A->plan && !A->plan->nbr.empty();
-        if (comm && sync_transport(ctx)) {  // debug / in-process transport: exchange first, no overlap
-            CHECK(exchange_on(A->plan, v, s));
-            comm = false;
-        }
-        if (comm) {
-            HIPC(hipEventRecord(ctx->ev_fork, s));
-            HIPC(hipStreamWaitEvent(ctx->s_comm, ctx->ev_fork, 0));
-            CHECK(exchange_on(A->plan, v, ctx->s_comm));
-            HIPC(hipEventRecord(ctx->ev_join, ctx->s_comm));
-        }
-        overlapped();
-        if (comm) HIPC(hipStreamWaitEvent(s, ctx->ev_join, 0));
-        after();
-        HIPC(hipGetLastError());
-        return PAMG_OK;
-    };
     pamg::TbArgs ta;
     ta.nstages = S;
     ta.last_resid = true;
@@ -2677,8 +2931,8 @@ int sweeps_part(pamg_ctx* ctx, const pamg_mat* A, int S, const double* in0, doub
         const int op = q == S - 1 ? pamg::OP_RESID : pamg::OP_JACOBI;
         const double w = q == S - 1 ? 0.0 : omega;
         double* v = const_cast<double*>(q == 0 ? in0 : out[q - 1]);
-        CHECK(stage(
-            v,
+        CHECK(overlap_exchange(
+            ctx, exch ? A->plan : nullptr, v,
             [&]() {
                 if (q == 0) pamg::launch_sym_tb(*A, ta, s);
                 // the set's planes next to the neighbour parts, both sides in one launch
@@ -2692,6 +2946,64 @@ int sweeps_part(pamg_ctx* ctx, const pamg_mat* A, int S, const double* in0, doub
 int jr_part(pamg_ctx* ctx, const pamg_mat* A, double* x, const double* b, double* t, double* r, double omega) {
     double* out[2] = {t, r};
     return sweeps_part(ctx, A, 2, x, out, b, omega);
+}
+
+// Which temporally blocked pass (Options::jr_fuse) a Jacobi sweep followed by the residual takes
+// on A: 1 — the whole one-part grid stencil in one launch (k_sym_tb, S = 2); 2 — one part of
+// several, the blocked pass on the slab's inner planes (jr_part); 0 — none.
+int jr_blocked(const pamg_mat* A) {
+    if (!pamg::options().jr_fuse || !A->interior.sym) return 0;
+    if (A->sym.tb_ok && !(A->plan && !A->plan->nbr.empty())) return 1;
+    return A->sym.tb_part ? 2 : 0;
+}
+
+// t = the weighted-Jacobi sweep from x, r = b - A t: the blocked pass jr_blocked names, else two
+// sweeps; *fused tells which. Enqueued on the compute stream.
+int jacobi_residual(pamg_ctx* ctx, const pamg_mat* A, double* x, const double* b, double* t, double* r, double omega,
+                    bool* fused) {
+    const int blocked = jr_blocked(A);
+    *fused = blocked != 0;
+    if (blocked == 2) return jr_part(ctx, A, x, b, t, r, omega);
+    if (blocked == 1) {
+        pamg::TbArgs ta;
+        ta.nstages = 2;
+        ta.last_resid = true;
+        ta.in0 = x;
+        ta.out[0] = t;
+        ta.out[1] = r;
+        ta.b = b;
+        ta.omega = omega;
+        pamg::launch_sym_tb(*A, ta, ctx->s_comp);
+        HIPC(hipGetLastError());
+        return PAMG_OK;
+    }
+    CHECK(apply(ctx, A, pamg::OP_JACOBI, x, b, t, omega));
+    return apply(ctx, A, pamg::OP_RESID, t, b, r, 0.0);
+}
+
+// Average milliseconds of `reps` calls of once() on stream s, after one warm-up call. once()
+// returns a status; the first failure (of a call, an event or a launch) is returned, the events
+// destroyed either way.
+template <class F>
+int time_reps(hipStream_t s, int reps, double* avg_ms, F&& once) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0.f;
+    const int rc = [&]() -> int {
+        HIPC(hipEventCreate(&e0));
+        HIPC(hipEventCreate(&e1));
+        CHECK(once());
+        HIPC(hipEventRecord(e0, s));
+        for (int k = 0; k < reps; ++k) CHECK(once());
+        HIPC(hipEventRecord(e1, s));
+        HIPC(hipEventSynchronize(e1));
+        HIPC(hipEventElapsedTime(&ms, e0, e1));
+        HIPC(hipGetLastError());
+        return PAMG_OK;
+    }();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    *avg_ms = ms / reps;
+    return rc;
 }
 
 // The deterministic dot x.y over the own rows of every rank (fixed-grid partials, then the
@@ -2904,12 +3216,9 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
             continue;
         }
         // level 0, V(1, nu2) from a given guess: the pre-smoothing sweep and the residual in one
-        // temporally blocked pass (k_sym_tb, S = 2; both timed as jacobi_pre)
-        const bool fuse = !cheb && l == 0 && !zero0 && H->nu1 == 1 && pamg::options().jr_fuse && A->interior.sym &&
-                          A->sym.tb_ok && !(A->plan && !A->plan->nbr.empty());
-        // one part of several: the blocked pass on the slab's inner planes (jr_part)
-        const bool fuse_part = !cheb && !fuse && l == 0 && !zero0 && H->nu1 == 1 && pamg::options().jr_fuse &&
-                               A->interior.sym && A->sym.tb_part;
+        // temporally blocked pass where the operator has one (jacobi_residual; both timed as
+        // jacobi_pre)
+        const bool fuse = !cheb && l == 0 && !zero0 && H->nu1 == 1 && jr_blocked(A) != 0;
         if (cheb) {
             ProfScope p(H, l, 0, s);
             double* in = l == 0 && !zero0 ? H->x[0] : nullptr;
@@ -2931,21 +3240,10 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
             double* oth[4];
             others(l, c, oth);
             o = oth[0];
-        } else if (fuse_part) {
-            ProfScope p(H, l, 0, s);
-            CHECK(jr_part(ctx, A, H->x[0], H->b[0], c, o, H->omega[0]));
         } else if (fuse) {
             ProfScope p(H, l, 0, s);
-            pamg::TbArgs ta;
-            ta.nstages = 2;
-            ta.last_resid = true;
-            ta.in0 = H->x[0];
-            ta.out[0] = c;
-            ta.out[1] = o;
-            ta.b = H->b[0];
-            ta.omega = H->omega[0];
-            pamg::launch_sym_tb(*A, ta, s);
-            HIPC(hipGetLastError());
+            bool fused = false;
+            CHECK(jacobi_residual(ctx, A, H->x[0], H->b[0], c, o, H->omega[0], &fused));
         } else {
             ProfScope p(H, l, 0, s);
             if (l == 0 && !zero0)
@@ -2959,7 +3257,7 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
         }
         cur[l] = c;
         spare[l] = o;
-        if (!fuse && !fuse_part) {
+        if (!fuse) {
             ProfScope p(H, l, 1, s);
             CHECK(apply(ctx, A, pamg::OP_RESID, c, H->b[l], o, 0.0));
         }
@@ -3544,10 +3842,7 @@ int pamg_exchange_begin(pamg_ctx* ctx, pamg_plan* plan, pamg_vec* x) {
         return PAMG_OK;
     }
     if (!plan->ev_done) HIPC(hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
-    HIPC(hipEventRecord(ctx->ev_fork, ctx->s_comp));
-    HIPC(hipStreamWaitEvent(ctx->s_comm, ctx->ev_fork, 0));
-    CHECK(exchange_on(plan, x->d, ctx->s_comm));
-    HIPC(hipEventRecord(plan->ev_done, ctx->s_comm));
+    CHECK(exchange_fork(ctx, plan, x->d, plan->ev_done));
     plan->in_flight = x;
     return PAMG_OK;
 }
@@ -3679,7 +3974,7 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
     // columns. (Sequential: the gaps depend on the row order.) Computed when a layout that
     // uses it is tried (the symmetric layout, tiles): not for rows that all go to ELL / pnc.
     int64_t band = -1;
-    auto get_band = [&]() -> int64_t {
+    const std::function<int64_t()> get_band = [&]() -> int64_t {
         if (band >= 0) return band;
         band = 0;
         std::vector<int> max_gap = column_reuse_gaps(rp, ci, nrows, n_own_cols);
@@ -3700,37 +3995,13 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
         tr.mark("band");
         return band;
     };
-    if (pamg::options().sym_dia && n_own_cols == nrows && has_all_diag && !inner.empty())
-        CHECK(build_sym_dia(A.get(), rp, ci, val, inner, get_band));
-    if (A->interior.sym) inner.clear();  // the interior rows run in k_rows_sym, not in tiles
-    tr.mark("sym dia");
-    // square operators (offsets from the row) and restrictions (fewer rows than columns; offsets from
-    // each row's first column)
-    // (several parts: the interior rows, when they are >= 3/4 of the operator — a 512^3 z-slab part's level 1)
-    // restrictions whose rows repeat few patterns (an aggregate shape each): pattern-dictionary rows
-    if (pamg::options().rpat && !A->interior.sym && n_own_cols > nrows && nrows > 0 &&
-        (int64_t)inner.size() * 4 >= (int64_t)nrows * 3) {
-        CHECK(build_rpat(A.get(), rp, ci, val, inner));
-        if (A->interior.rpat) inner.clear();  // the rows run in k_rows_rpat, not in tiles
-        tr.mark("rpat");
-    }
-    if (pamg::options().ell && !A->interior.sym && !A->interior.rpat && n_own_cols >= nrows && nrows > 0 &&
-        (int64_t)inner.size() * 4 >= (int64_t)nrows * 3 && nrows >= pamg::options().ell_min_rows &&
-        (n_own_cols == nrows || pamg::options().ell_restrict)) {
-        CHECK(build_ell(A.get(), rp, ci, val, n_own_cols != nrows, inner));
-        if (A->interior.ell) inner.clear();  // the rows run in k_rows_ell, not in tiles
-        tr.mark("ell");
-    }
-    // a prolongation over a 7-point grid uploaded earlier on this context: neighbour-coded rows
-    if (pamg::options().pnc && n_own_cols < nrows && (int64_t)inner.size() * 4 >= (int64_t)nrows * 3) {
-        // (every registered grid of this row count, the latest first: grids of one size but other
-        // shapes may be registered too, and the neighbour check decides)
-        const auto grids = grids_of(ctx);
-        for (auto g = grids.rbegin(); g != grids.rend() && !A->interior.pnc; ++g)
-            if ((*g)[0] == nrows) CHECK(build_pnc(A.get(), rp, ci, val, *g, inner));
-        if (A->interior.pnc) inner.clear();  // the rows run in k_rows_pnc, not in tiles
-        tr.mark("pnc");
-    }
+    // the layout families in their fixed order: each takes the interior rows left (and clears the
+    // list) or declines
+    Upload u{A.get(), rp, ci, val, n_own_cols, has_all_diag, inner, bnd, get_band, tr};
+    CHECK(sym_try(u));
+    CHECK(rpat_try(u));
+    CHECK(ell_try(u));
+    CHECK(pnc_try(u));
     // the CSR copies: read by the tile and long-row kernels only, so not uploaded when every row
     // runs in the symmetric, ELL or neighbour-coded layout (the 512^3 A0, A1, R0, P0: 29 GB less)
     if (!inner.empty() || !bnd.empty()) {
@@ -3751,86 +4022,10 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
         CHECK(h2d(ctx, A->d_diag, diag.data(), sizeof(double) * nrows));
     }
     tr.mark("csr copies");
-    std::vector<uint16_t> lo;
-    std::vector<uint8_t> hi, vidx;
-    {
-        std::vector<int4> t_in, t_bd;
-        const bool square = n_own_cols == nrows;
-        const bool tall = n_own_cols < nrows;  // a prolongation's shape
-        const int64_t tb = inner.empty() && bnd.empty() ? 0 : get_band();
-        CHECK(build_tiles(rp, inner, square, &A->interior, tb, ci, &lo, &hi, val, &vidx, &t_in, tall));
-        CHECK(build_tiles(rp, bnd, square, &A->boundary, tb, ci, &lo, &hi, val, &vidx, &t_bd, tall));
-        tr.mark("tiles");
-        std::vector<uint8_t> idx8;
-        CHECK(build_col_dicts(A.get(), rp, ci, t_in, t_bd, &idx8));
-        tr.mark("col dicts");
-        CHECK(build_tile_major(A.get(), n_own_cols, rp, ci, val, t_in, t_bd, lo, hi, idx8));
-        tr.mark("tile-major");
-    }
-    if (A->interior.rl8 || A->boundary.rl8) {
-        std::vector<uint8_t> rl(nrows + kVecPad, 0);
-        par_for(nrows, [&](int64_t a, int64_t b) {
-            for (int64_t i = a; i < b; ++i) rl[i] = (uint8_t)std::min<int64_t>(255, rp[i + 1] - rp[i]);
-        });
-        CHECK(dalloc(&A->d_rlen, nrows + kVecPad));
-        CHECK(h2d(ctx, A->d_rlen, rl.data(), rl.size()));
-    }
-    if (!vidx.empty()) {
-        CHECK(dalloc(&A->d_vidx, (int64_t)vidx.size()));
-        CHECK(h2d(ctx, A->d_vidx, vidx.data(), vidx.size()));
-    }
-    // the bytes one apply streams, per tile set: long rows (row pointer, 12 B/nonzero, list
-    // entry) + short tiles in their layout — row bounds (1 B/row with 8-bit lengths, else 4-B
-    // row pointers), columns (4 B; 3 B 24-bit; cd/8 B with a dictionary + its 4-B offsets),
-    // values (8 B; or a 4-bit index + the tile's 128-B table), 16-B descriptors (+ a 4-B
-    // column base with 24-bit columns); a tile-major set streams whole padded slots
-    // (tile_nnz values and column entries, tm_rs row lengths per tile). + the closing pointer.
-    A->stream_bytes = 4;
-    // symmetric diagonal-class layout: 8/16-bit mask, diagonal and nu upper values per row (the
-    // mirrored lower values are the same lines, re-read from cache)
-    if (A->interior.sym)
-        A->stream_bytes += A->sym.vd_n ? nrows + (int64_t)A->sym.vd_n * (8 * (A->sym.nu + 1) + 4)
-                                       : nrows * (A->sym.mask_bytes + 8 + 8 * (int64_t)A->sym.nu);
-    // sliced ELL: two index bytes per padded nonzero, a length byte per row, the slice and group
-    // descriptors and the group tables
-    if (A->interior.ell)
-        A->stream_bytes += (A->ell.paired ? 4 : 8) * A->ell.words + nrows + 8 * A->ell.nslices + 16 * A->ell.ngroups + 4 * A->ell.otab_n +
-                           8 * A->ell.vtab_n + (A->ell.d_anc ? 4 * nrows : 0) +
-                           (A->ell.win ? 32 * A->ell.ngroups + 8 * A->ell.nchunks + 2 * A->ell.lof_n + nrows : 0);
-    // neighbour-coded prolongation: the anchor and the record per row, the two tables
-    if (A->interior.pnc)
-        A->stream_bytes += (A->pnc.d_cid ? 6 : 12) * nrows + (A->pnc.d_cid ? 12 : 4) * A->pnc.npat + 8 * A->pnc.nval;
-    // pattern-dictionary rows: the first column and the pattern id per row, the tables
-    if (A->interior.rpat) A->stream_bytes += 5 * nrows + 8 * A->rpat.npat + 4 * A->rpat.nent + 8 * A->rpat.nval;
-    for (const pamg::TileSet* t : {&A->interior, &A->boundary}) {
-        if (t->sym || t->ell || t->pnc || t->rpat) continue;  // counted above
-        const int64_t ns = t->n_short, nz = t->nnz_short;
-        int64_t b = 8 * (int64_t)t->n_long + 12 * t->nnz_long;
-        const bool base = t->c24 && !t->cd;
-        if (t->tm) {  // whole padded slots: tile_nnz values + column entries + tm_rs lengths
-            const int64_t tn = t->tile_nnz;
-            const int64_t rowb = t->tm_rs;
-            const int64_t valb = t->tm_vt ? tn + 8 * (int64_t)t->tm_vt : 8 * tn;  // 8-bit indices + table
-            b += ns * (rowb * (t->anc ? 5 : 1) + valb + (t->cd ? t->cd * tn / 8 : 3 * tn) + 16 + (base ? 4 : 0)) +
-                 (t->cd ? 4 * t->ctab_n * (t->pt ? ns : 1) : 0);
-        } else {
-            b += (t->rl8 ? 1 : 4) * t->rows_short;
-            b += t->cd ? (t->cd * nz + 7) / 8 + 4 * t->ctab_n * (t->pt ? ns : 1) : (t->c24 ? 3 : 4) * nz;
-            if (t->pt && t->anc) b += 2 * t->rows_short + 4 * ns;  // 16-bit anchors + tile bases
-            b += t->vd ? nz / 2 + 128 * ns : 8 * nz;
-            b += (16 + (base ? 4 : 0)) * ns;
-        }
-        A->stream_bytes += b;
-    }
-    if (!lo.empty()) {  // padded like d_col
-        lo.resize(nnz + kVecPad, 0);
-        hi.resize(nnz + kVecPad, 0);
-        CHECK(dalloc(&A->d_clo, nnz + kVecPad));
-        CHECK(dalloc(&A->d_chi, nnz + kVecPad));
-        CHECK(h2d(ctx, A->d_clo, lo.data(), sizeof(uint16_t) * lo.size()));
-        CHECK(h2d(ctx, A->d_chi, hi.data(), sizeof(uint8_t) * hi.size()));
-    }
-    tr.mark("rest");
+    CHECK(tiles_try(u));
+    // the bytes one apply streams: every family's share + the closing pointer
+    A->stream_bytes = 4 + sym_bytes(A.get()) + ell_bytes(A.get()) + pnc_bytes(A.get()) + rpat_bytes(A.get()) +
+                      tiles_bytes(A.get());
     *out = A.release();
     return PAMG_OK;
 }
@@ -3913,17 +4108,12 @@ int pamg_mat_destroy(pamg_mat* A) {
     dfree(A->d_anc16);
     dfree(A->d_val);
     dfree(A->d_diag);
-    dfree(A->sym.d_mask);
-    dfree(A->sym.d_diag);
-    dfree(A->sym.d_upper);
-    dfree(A->sym.d_tid);
-    dfree(A->sym.d_vtab);
-    dfree(A->sym.d_mtab);
-    free_tiles(A->interior);
-    free_tiles(A->boundary);
-    free_ell(A->ell);
-    free_pnc(A->pnc);
-    free_rpat(A->rpat);
+    sym_free(A->sym);
+    tiles_free(A->interior);
+    tiles_free(A->boundary);
+    ell_free(A->ell);
+    pnc_free(A->pnc);
+    rpat_free(A->rpat);
     pamg_ctx* owner = A->ctx;
     delete A;
     ctx_unref(owner);
@@ -3947,56 +4137,17 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes) {
 int pamg_mat_layout(const pamg_mat* A, int set, int out[10]) {
     if (!A || !out || set < 0 || set > 1) return fail(PAMG_E_ARG, "mat_layout: bad args");
     const pamg::TileSet& t = set == 0 ? A->interior : A->boundary;
-    out[0] = t.c24;
-    out[1] = t.vd;
-    out[2] = t.rl8;
-    out[3] = t.cd;
-    out[4] = t.ctab_n;
-    out[5] = t.tm;
-    out[6] = t.tm_rs;
-    out[7] = t.tile_nnz;
-    out[8] = t.n_short;
-    out[9] = (t.anc ? 1 : 0) | (t.pt ? 2 : 0) | (t.xs ? 4 : 0) | (t.sym ? 8 : 0) | (t.sym && A->sym.rpl == 2 ? 16 : 0) |
-             (t.sym && (A->sym.tb_ok || A->sym.tb_part) ? 32 : 0) | (t.tm && t.tm_vt ? 64 : 0) |
-             (t.sym && A->sym.vd_n ? 128 : 0) | (t.ell ? 512 : 0) | (t.pnc ? 1024 : 0) | (t.rpat ? 2048 : 0) |
-             (t.pnc && A->pnc.d_cid ? 4096 : 0) | (t.ell && A->ell.paired ? 8192 : 0);
-    if (t.ell) out[8] = (int)A->ell.ngroups;  // k_rows_ell's grid
-    if (t.rpat) {  // the pattern and value tables, k_rows_rpat's grid
-        out[3] = A->rpat.nval;
-        out[4] = A->rpat.npat;
-        out[8] = (int)A->rpat.ngroups;
-    }
-    if (t.pnc) {  // the pattern and value tables, k_rows_pnc's grid
-        out[3] = A->pnc.nval;
-        out[4] = A->pnc.npat;
-        out[8] = A->pnc.grid;
-    }
-    if (t.sym) {  // the symmetric diagonal-class layout: upper classes, k_rows_sym's grid
-        out[4] = A->sym.nu;
-        out[8] = A->sym.nbands * 8 * A->sym.eighth;
-    }
+    tiles_report(A, t, out);  // every slot; the family that holds the set overrides its own
+    ell_report(A, t, out);
+    rpat_report(A, t, out);
+    pnc_report(A, t, out);
+    sym_report(A, t, out);
     return PAMG_OK;
 }
 
 int pamg_mat_ell_window(const pamg_mat* A, int out[16]) {
     if (!A || !out) return fail(PAMG_E_ARG, "mat_ell_window: bad args");
-    const pamg::EllSet& E = A->ell;
-    const bool w = A->interior.ell && E.win;
-    out[0] = w ? 1 : 0;
-    out[1] = w ? E.win_groups : 0;
-    out[2] = w ? E.gather_groups : 0;
-    out[3] = w ? E.max_window : 0;
-    out[4] = w ? E.noncontig_groups : 0;
-    out[5] = w ? E.max_pairs : 0;
-    out[6] = w ? E.max_chunks : 0;
-    out[7] = w ? (int)E.ngroups : 0;
-    out[8] = w ? E.mean_window : 0;
-    out[9] = w ? E.p95_window : 0;
-    out[10] = w ? E.mean_runs : 0;
-    out[11] = w ? E.max_runs : 0;
-    out[12] = w ? E.mean_pairs : 0;
-    out[13] = w ? E.full_groups : 0;
-    out[14] = out[15] = 0;
+    ell_window(A, out);
     return PAMG_OK;
 }
 
@@ -4066,26 +4217,9 @@ int pamg_jacobi_residual(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pa
     if (b->n_own != A->nrows || r->n_own != A->nrows || t == x || r == x || r == t || b == t || b == r)
         return fail(PAMG_E_ARG, "jacobi_residual: size mismatch or aliasing");
     CHECK(set_device(ctx));
-    const bool fuse = pamg::options().jr_fuse && A->interior.sym && A->sym.tb_ok && !(A->plan && !A->plan->nbr.empty());
-    const bool fuse_part = !fuse && pamg::options().jr_fuse && A->interior.sym && A->sym.tb_part;
-    if (fuse_part) {
-        CHECK(jr_part(ctx, A, x->d, b->d, t->d, r->d, omega));
-    } else if (fuse) {
-        pamg::TbArgs ta;
-        ta.nstages = 2;
-        ta.last_resid = true;
-        ta.in0 = x->d;
-        ta.out[0] = t->d;
-        ta.out[1] = r->d;
-        ta.b = b->d;
-        ta.omega = omega;
-        pamg::launch_sym_tb(*A, ta, ctx->s_comp);
-        HIPC(hipGetLastError());
-    } else {
-        CHECK(apply(ctx, A, pamg::OP_JACOBI, x->d, b->d, t->d, omega));
-        CHECK(apply(ctx, A, pamg::OP_RESID, t->d, b->d, r->d, 0.0));
-    }
-    if (fused) *fused = (fuse || fuse_part) ? 1 : 0;
+    bool did_fuse = false;
+    CHECK(jacobi_residual(ctx, A, x->d, b->d, t->d, r->d, omega, &did_fuse));
+    if (fused) *fused = did_fuse ? 1 : 0;
     HIPC(hipStreamSynchronize(ctx->s_comp));
     return PAMG_OK;
 }
@@ -4709,89 +4843,79 @@ int pamg_pcg(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* b, double
     return PAMG_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The option keys of pamg_set_option / pamg_get_option: the Options member (pamg_device.h
+// documents each) and the values accepted, lo <= value <= hi, powers of two only where pow2.
+struct OptionRow {
+    const char* key;
+    int pamg::Options::*member;
+    int64_t lo, hi;
+    bool pow2;
+};
+using O = pamg::Options;
+const OptionRow kOptionTable[] = {
+    {"tile_nnz", &O::tile_nnz, 1024, 4096, true},
+    {"tile_order", &O::tile_order, 0, 1, false},  // 0 natural, 1 banded XCD-blocked
+    {"poison_ghosts", &O::poison_ghosts, 0, 1, false},
+    {"col24", &O::col24, 0, 1, false},
+    {"long_tiles", &O::long_tiles, 0, 1, false},
+    {"row_len8", &O::row_len8, 0, 1, false},
+    {"value_dict", &O::value_dict, 0, 2, false},
+    {"col_dict", &O::col_dict, 0, 1, false},
+    {"tile_major", &O::tile_major, 0, 2, false},
+    {"col_dict_anchor", &O::col_dict_anchor, 0, 1, false},
+    {"col_dict_tile", &O::col_dict_tile, 0, 1, false},
+    {"x_stage", &O::x_stage, 0, 1, false},
+    {"band_pct", &O::band_pct, 1, 10000, false},
+    {"band_pct_restrict", &O::band_pct_restrict, 1, 10000, false},
+    {"long_tiles_min", &O::long_tiles_min, 1, 255, false},
+    {"tm_tile_dicts", &O::tm_tile_dicts, 0, 1, false},
+    {"sym_dia", &O::sym_dia, 0, 1, false},
+    {"sym_rows", &O::sym_rows, 1, 2, false},
+    {"jr_fuse", &O::jr_fuse, 0, 1, false},
+    {"sym_vd", &O::sym_vd, 0, 1, false},
+    {"symd_chunks", &O::symd_chunks, 1, 4, true},
+    {"sym_zm", &O::sym_zm, 0, 1, false},
+    {"tb_xfast", &O::tb_xfast, 0, 1, false},
+    {"ell", &O::ell, 0, 1, false},
+    {"ell_restrict", &O::ell_restrict, 0, 1, false},
+    {"pnc", &O::pnc, 0, 1, false},
+    {"rpat", &O::rpat, 0, 1, false},
+    {"pnc_compact", &O::pnc_compact, 0, 1, false},
+    {"ell_pair", &O::ell_pair, 0, 1, false},
+    {"ell_xwin", &O::ell_xwin, 0, 1, false},
+    {"ell_xwin_max", &O::ell_xwin_max, 2, pamg::kEllWinCap, false},
+    {"ell_yblock", &O::ell_yblock, 0, 65536, false},
+    {"ell_min_rows", &O::ell_min_rows, 0, INT32_MAX, false},
+    {"zm_chunks", &O::zm_chunks, 0, 4096, false},
+    {"chain_store_x", &O::chain_store_x, 0, 1, false},
+};
+
+const OptionRow* find_option(const char* key) {
+    for (const OptionRow& r : kOptionTable)
+        if (std::strcmp(r.key, key) == 0) return &r;
+    return nullptr;
+}
+}  // namespace
+
+extern "C" {
+
 int pamg_set_option(const char* key, int64_t value) {
     if (!key) return fail(PAMG_E_ARG, "set_option: NULL key");
-    auto& o = pamg::options();
-    const std::string k(key);
-    if (k == "tile_nnz" && (value == 1024 || value == 2048 || value == 4096)) o.tile_nnz = (int)value;
-    else if (k == "tile_order" && (value == 0 || value == 1)) o.tile_order = (int)value;  // 0 natural, 1 banded XCD-blocked
-    else if (k == "poison_ghosts" && (value == 0 || value == 1)) o.poison_ghosts = (int)value;
-    else if (k == "col24" && (value == 0 || value == 1)) o.col24 = (int)value;
-    else if (k == "long_tiles" && (value == 0 || value == 1)) o.long_tiles = (int)value;
-    else if (k == "row_len8" && (value == 0 || value == 1)) o.row_len8 = (int)value;
-    else if (k == "value_dict" && value >= 0 && value <= 2) o.value_dict = (int)value;
-    else if (k == "col_dict" && (value == 0 || value == 1)) o.col_dict = (int)value;
-    else if (k == "tile_major" && value >= 0 && value <= 2) o.tile_major = (int)value;
-    else if (k == "col_dict_anchor" && (value == 0 || value == 1)) o.col_dict_anchor = (int)value;
-    else if (k == "col_dict_tile" && (value == 0 || value == 1)) o.col_dict_tile = (int)value;
-    else if (k == "x_stage" && (value == 0 || value == 1)) o.x_stage = (int)value;
-    else if (k == "band_pct" && value >= 1 && value <= 10000) o.band_pct = (int)value;
-    else if (k == "band_pct_restrict" && value >= 1 && value <= 10000) o.band_pct_restrict = (int)value;
-    else if (k == "long_tiles_min" && value >= 1 && value <= 255) o.long_tiles_min = (int)value;
-    else if (k == "tm_tile_dicts" && (value == 0 || value == 1)) o.tm_tile_dicts = (int)value;
-    else if (k == "sym_dia" && (value == 0 || value == 1)) o.sym_dia = (int)value;
-    else if (k == "sym_rows" && (value == 1 || value == 2)) o.sym_rows = (int)value;
-    else if (k == "jr_fuse" && (value == 0 || value == 1)) o.jr_fuse = (int)value;
-    else if (k == "sym_vd" && (value == 0 || value == 1)) o.sym_vd = (int)value;
-    else if (k == "symd_chunks" && (value == 1 || value == 2 || value == 4)) o.symd_chunks = (int)value;
-    else if (k == "sym_zm" && (value == 0 || value == 1)) o.sym_zm = (int)value;
-    else if (k == "tb_xfast" && (value == 0 || value == 1)) o.tb_xfast = (int)value;
-    else if (k == "ell" && (value == 0 || value == 1)) o.ell = (int)value;
-    else if (k == "ell_restrict" && (value == 0 || value == 1)) o.ell_restrict = (int)value;
-    else if (k == "pnc" && (value == 0 || value == 1)) o.pnc = (int)value;
-    else if (k == "rpat" && (value == 0 || value == 1)) o.rpat = (int)value;
-    else if (k == "pnc_compact" && (value == 0 || value == 1)) o.pnc_compact = (int)value;
-    else if (k == "ell_pair" && (value == 0 || value == 1)) o.ell_pair = (int)value;
-    else if (k == "ell_xwin" && (value == 0 || value == 1)) o.ell_xwin = (int)value;
-    else if (k == "ell_xwin_max" && value >= 2 && value <= pamg::kEllWinCap) o.ell_xwin_max = (int)value;
-    else if (k == "ell_yblock" && value >= 0 && value <= 65536) o.ell_yblock = (int)value;
-    else if (k == "ell_min_rows" && value >= 0 && value <= INT32_MAX) o.ell_min_rows = (int)value;
-    else if (k == "zm_chunks" && value >= 0 && value <= 4096) o.zm_chunks = (int)value;
-    else if (k == "chain_store_x" && (value == 0 || value == 1)) o.chain_store_x = (int)value;
-    else return fail(PAMG_E_ARG, "set_option: unknown key or bad value: %s=%lld", key, (long long)value);
+    const OptionRow* r = find_option(key);
+    if (!r || value < r->lo || value > r->hi || (r->pow2 && (value & (value - 1)) != 0))
+        return fail(PAMG_E_ARG, "set_option: unknown key or bad value: %s=%lld", key, (long long)value);
+    pamg::options().*(r->member) = (int)value;
     return PAMG_OK;
 }
 
 int pamg_get_option(const char* key, int64_t* value) {
     if (!key || !value) return fail(PAMG_E_ARG, "get_option: bad args");
-    const auto& o = pamg::options();
-    const std::string k(key);
-    if (k == "tile_nnz") *value = o.tile_nnz;
-    else if (k == "tile_order") *value = o.tile_order;
-    else if (k == "long_tiles") *value = o.long_tiles;
-    else if (k == "row_len8") *value = o.row_len8;
-    else if (k == "poison_ghosts") *value = o.poison_ghosts;
-    else if (k == "col24") *value = o.col24;
-    else if (k == "value_dict") *value = o.value_dict;
-    else if (k == "col_dict") *value = o.col_dict;
-    else if (k == "tile_major") *value = o.tile_major;
-    else if (k == "col_dict_anchor") *value = o.col_dict_anchor;
-    else if (k == "col_dict_tile") *value = o.col_dict_tile;
-    else if (k == "x_stage") *value = o.x_stage;
-    else if (k == "band_pct") *value = o.band_pct;
-    else if (k == "band_pct_restrict") *value = o.band_pct_restrict;
-    else if (k == "long_tiles_min") *value = o.long_tiles_min;
-    else if (k == "tm_tile_dicts") *value = o.tm_tile_dicts;
-    else if (k == "sym_dia") *value = o.sym_dia;
-    else if (k == "sym_rows") *value = o.sym_rows;
-    else if (k == "jr_fuse") *value = o.jr_fuse;
-    else if (k == "sym_vd") *value = o.sym_vd;
-    else if (k == "symd_chunks") *value = o.symd_chunks;
-    else if (k == "sym_zm") *value = o.sym_zm;
-    else if (k == "tb_xfast") *value = o.tb_xfast;
-    else if (k == "ell") *value = o.ell;
-    else if (k == "ell_restrict") *value = o.ell_restrict;
-    else if (k == "pnc") *value = o.pnc;
-    else if (k == "rpat") *value = o.rpat;
-    else if (k == "pnc_compact") *value = o.pnc_compact;
-    else if (k == "ell_pair") *value = o.ell_pair;
-    else if (k == "ell_xwin") *value = o.ell_xwin;
-    else if (k == "ell_xwin_max") *value = o.ell_xwin_max;
-    else if (k == "ell_yblock") *value = o.ell_yblock;
-    else if (k == "ell_min_rows") *value = o.ell_min_rows;
-    else if (k == "zm_chunks") *value = o.zm_chunks;
-    else if (k == "chain_store_x") *value = o.chain_store_x;
-    else return fail(PAMG_E_ARG, "get_option: unknown key %s", key);
+    const OptionRow* r = find_option(key);
+    if (!r) return fail(PAMG_E_ARG, "get_option: unknown key %s", key);
+    *value = pamg::options().*(r->member);
     return PAMG_OK;
 }
 
@@ -4802,21 +4926,13 @@ int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps
     CHECK(check_vec_for(H->A[0], x, "hier_bench_chain"));
     CHECK(set_device(ctx));
     CHECK(ensure_u0(H));
-    hipEvent_t e0, e1;
-    HIPC(hipEventCreate(&e0));
-    HIPC(hipEventCreate(&e1));
-    hipStream_t s = ctx->s_comp;
-    CHECK(launch_chain3(H, x->d, b->d, H->t[0], H->u0));
-    HIPC(hipEventRecord(e0, s));
-    for (int k = 0; k < reps; ++k) CHECK(launch_chain3(H, x->d, b->d, (k & 1) ? H->u0 : H->t[0], (k & 1) ? H->t[0] : H->u0));
-    HIPC(hipEventRecord(e1, s));
-    HIPC(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return PAMG_OK;
+    // the warm-up call and the even timed ones t[0] -> u0, the odd ones u0 -> t[0]
+    int k = -1;  // (the warm-up call)
+    return time_reps(ctx->s_comp, reps, avg_ms, [&]() {
+        const bool back = k > 0 && (k & 1);
+        ++k;
+        return launch_chain3(H, x->d, b->d, back ? H->u0 : H->t[0], back ? H->t[0] : H->u0);
+    });
 }
 
 int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, const pamg_vec* b,
@@ -4835,27 +4951,14 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
         double* xo = nullptr;
         CHECK(dalloc(&xo, A->nrows + kVecPad));
         int rc = dzero(ctx, xo, sizeof(double) * (size_t)(A->nrows + kVecPad));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
         hipStream_t s = ctx->s_comp;
-        auto once = [&]() {
-            pamg::launch_rows(*A, A->interior, op, x->d, b->d, xo, y->d, omega, s, omega);
-            pamg::launch_rows(*A, A->boundary, op, x->d, b->d, xo, y->d, omega, s, omega);
-        };
-        float ms = 0.f;
-        if (rc == PAMG_OK && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = PAMG_E_HIP;
-        if (rc == PAMG_OK) {
-            once();
-            (void)hipEventRecord(e0, s);
-            for (int k = 0; k < reps; ++k) once();
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess ||
-                hipGetLastError() != hipSuccess)
-                rc = fail(PAMG_E_HIP, "bench_rowop: op 6 failed");
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
+        if (rc == PAMG_OK)
+            rc = time_reps(s, reps, avg_ms, [&]() {
+                pamg::launch_rows(*A, A->interior, op, x->d, b->d, xo, y->d, omega, s, omega);
+                pamg::launch_rows(*A, A->boundary, op, x->d, b->d, xo, y->d, omega, s, omega);
+                return PAMG_OK;
+            });
         dfree(xo);
-        *avg_ms = ms / reps;
         return rc;
     }
     if (op >= 4 && !(A->interior.sym && (A->sym.tb_ok || A->sym.tb_part)))
@@ -4870,11 +4973,12 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
     // ops 4 / 5: the temporally blocked passes k_sym_tb<2> (Jacobi -> residual) and <3>
     // (Jacobi -> Jacobi -> residual), the first output into y, the others into scratch
     double* scratch[2] = {nullptr, nullptr};
+    int rc = PAMG_OK;
     if (op >= 4) {
         const int64_t len = part_tb ? (A->plan ? A->plan->n_own + A->plan->n_ghost : A->ncols) : A->nrows;
         for (double*& p : scratch) {
-            CHECK(dalloc(&p, std::max<int64_t>(len, A->nrows) + kVecPad));
-            CHECK(dzero(ctx, p, sizeof(double) * (size_t)(std::max<int64_t>(len, A->nrows) + kVecPad)));
+            if (rc == PAMG_OK) rc = dalloc(&p, std::max<int64_t>(len, A->nrows) + kVecPad);
+            if (rc == PAMG_OK) rc = dzero(ctx, p, sizeof(double) * (size_t)(std::max<int64_t>(len, A->nrows) + kVecPad));
         }
     }
     pamg::TbArgs ta;
@@ -4888,33 +4992,22 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
     ta.out[2] = scratch[1];
     ta.b = b ? b->d : nullptr;
     ta.omega = omega;
-    hipEvent_t e0, e1;
-    HIPC(hipEventCreate(&e0));
-    HIPC(hipEventCreate(&e1));
     hipStream_t s = ctx->s_comp;
     const double* bd = b ? b->d : nullptr;
-    auto once = [&]() {
-        if (op >= 4 && A->sym.tb_part) {  // one part of several: its blocked pass + edge planes + boundary rows
-            (void)sweeps_part(ctx, A, op - 2, x->d, ta.out, ta.b, omega, false);
-        } else if (op >= 4) {
-            pamg::launch_sym_tb(*A, ta, s);
-        } else {
-            pamg::launch_rows(*A, A->interior, op, x->d, bd, x->d, y->d, omega, s);
-            pamg::launch_rows(*A, A->boundary, op, x->d, bd, x->d, y->d, omega, s);
-        }
-    };
-    once();
-    HIPC(hipEventRecord(e0, s));
-    for (int k = 0; k < reps; ++k) once();
-    HIPC(hipEventRecord(e1, s));
-    HIPC(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, e0, e1));
-    *avg_ms = ms / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (rc == PAMG_OK)
+        rc = time_reps(s, reps, avg_ms, [&]() {
+            if (op >= 4 && A->sym.tb_part)  // one part of several: its blocked pass + edge planes + boundary rows
+                return sweeps_part(ctx, A, op - 2, x->d, ta.out, ta.b, omega, false);
+            if (op >= 4) {
+                pamg::launch_sym_tb(*A, ta, s);
+            } else {
+                pamg::launch_rows(*A, A->interior, op, x->d, bd, x->d, y->d, omega, s);
+                pamg::launch_rows(*A, A->boundary, op, x->d, bd, x->d, y->d, omega, s);
+            }
+            return (int)PAMG_OK;
+        });
     for (double* p : scratch) dfree(p);
-    return PAMG_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -115,7 +115,7 @@ OPTION_DEFAULTS = {"tile_nnz": (1024, 4096), "tile_order": (1, 0), "col24": (1, 
                    "sym_dia": (1, 0), "sym_rows": (2, 1), "jr_fuse": (1, 0), "sym_vd": (1, 0),
                    "symd_chunks": (2, 4), "chain_store_x": (0, 1), "sym_zm": (1, 0), "zm_chunks": (0, 16),
                    "tb_xfast": (1, 0), "ell": (1, 0), "ell_restrict": (1, 0), "ell_min_rows": (65536, 1024), "pnc": (1, 0), "rpat": (1, 0), "pnc_compact": (1, 0), "ell_pair": (1, 0),
-                   "ell_yblock": (16, 0)}
+                   "ell_yblock": (16, 0), "ell_xwin": (1, 0), "ell_xwin_max": (7168, 2816)}
 
 
 def test_option_keys_defaults_and_docs(built):
@@ -126,6 +126,15 @@ def test_option_keys_defaults_and_docs(built):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     integ = open(os.path.join(root, "INTEGRATION.md")).read()
     header = open(os.path.join(root, "include", "pamg.h")).read()
+    # the keys pamg_set_option accepts: the key column of the library's option table, which is
+    # also the key column of INTEGRATION.md's (a row may name several keys)
+    import re
+    table = open(os.path.join(root, "parallel_amg_amd", "csrc", "runtime.hip")).read()
+    accepted = set(re.findall(r'^\s*\{"(\w+)", &O::\1,', table, re.M))
+    rows = integ.split("| key | default | meaning |\n|---|---|---|\n")[1].split("\n\n")[0].splitlines()
+    documented = {k for row in rows for k in re.findall(r"`(\w+)`", row.split("|")[1])}
+    assert set(OPTION_DEFAULTS) == accepted == documented, (
+        accepted ^ set(OPTION_DEFAULTS), documented ^ set(OPTION_DEFAULTS))
     v = C.c_int64()
     for k, (default, other) in OPTION_DEFAULTS.items():
         call("pamg_get_option", k.encode(), C.byref(v))

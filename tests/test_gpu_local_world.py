@@ -4,7 +4,6 @@ in-process world (pamg_world / pamg_comm_init_local), ghosts moved by device-to-
 from the sibling parts' vectors. The global-view oracle's multi-part setup (SPEC §S7) is the
 reference: b = A x*, x after V-cycles (bit for bit), residual histories and PCG (1e-12), with
 NaN-poisoned ghost slots before every exchange (a read before the copy landed would show)."""
-import contextlib
 import ctypes
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 
 import parallel_amg_amd as pa
 from oracle import oracle as O
-from parallel_amg_amd._lib import call, layout_of
+from parallel_amg_amd._lib import call, layout_of, option
 from parallel_amg_amd.partitioned import LocalWorld, PVector, consistent, mul
 from parallel_amg_amd.solver import AMGSolver
 
@@ -21,17 +20,6 @@ pytestmark = pytest.mark.gpu
 
 def bits(a):
     return np.asarray(a, np.float64).view(np.int64)
-
-
-@contextlib.contextmanager
-def option(key, value):
-    v = ctypes.c_int64()
-    call("pamg_get_option", key.encode(), ctypes.byref(v))
-    call("pamg_set_option", key.encode(), int(value))
-    try:
-        yield
-    finally:
-        call("pamg_set_option", key.encode(), v.value)
 
 
 @pytest.mark.parametrize("nparts,kind,n,max_coarse,agglomerate", [

@@ -8,6 +8,7 @@ import pytest
 import parallel_amg_amd as pa
 from oracle import oracle as O
 from parallel_amg_amd._lib import PamgError
+from parallel_amg_amd._lib import option as _with_option
 from parallel_amg_amd.hcsr import HCSR
 from parallel_amg_amd.partitioned import PSparseMatrix, PVector, axpby, dot, jacobi, mul, norm, residual
 from parallel_amg_amd.solver import AMGSolver
@@ -651,20 +652,11 @@ def test_per_tile_dictionaries_random(ctx, novd, name, ndist, lengths):
     assert lay["per_tile"] or lay["cd"] == 0, lay
 
 def _with_options(opts, fn):
-    import ctypes
-    from parallel_amg_amd._lib import call
-    old = {}
-    for k in opts:
-        v = ctypes.c_int64()
-        call("pamg_get_option", k.encode(), ctypes.byref(v))
-        old[k] = v.value
-    try:
+    import contextlib
+    with contextlib.ExitStack() as stack:
         for k, v in opts.items():
-            call("pamg_set_option", k.encode(), v)
+            stack.enter_context(_with_option(k, v))
         return fn()
-    finally:
-        for k, v in old.items():
-            call("pamg_set_option", k.encode(), v)
 
 
 # x_stage cases (name -> matrix, x staged?): clustered row-relative offsets — the stencils
@@ -926,23 +918,6 @@ def test_reorder_graph_equals_eager(ctx):
 
 
 # ---------------------------------------------------------------- symmetric diagonal-class layout
-def _with_option(key, value):
-    import contextlib
-    import ctypes
-    from parallel_amg_amd._lib import call
-
-    @contextlib.contextmanager
-    def cm():
-        v = ctypes.c_int64()
-        call("pamg_get_option", key.encode(), ctypes.byref(v))
-        call("pamg_set_option", key.encode(), value)
-        try:
-            yield
-        finally:
-            call("pamg_set_option", key.encode(), v.value)
-    return cm()
-
-
 def _sym_grid(kind, n, seed=None):
     """The SPEC grid operator, or (seed) the same pattern with random symmetric values;
     "p9": the 2D 9-point pattern (9 offsets: 16-bit row masks)."""

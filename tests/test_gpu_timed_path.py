@@ -21,14 +21,11 @@ pin the timed path at this size:
   and omega and the coarse inverse, bit for bit; and 3 oracle V-cycles on that independent
   hierarchy == the timed call (VERDICT r5 missing-3: setup parity at the metric's size).
 """
-import contextlib
-import ctypes
-
 import numpy as np
 import pytest
 
 import parallel_amg_amd as pa
-from parallel_amg_amd._lib import call, layout_of
+from parallel_amg_amd._lib import layout_of, option
 from parallel_amg_amd.partitioned import PVector, jacobi_residual, mul
 from parallel_amg_amd.solver import AMGSolver
 
@@ -37,17 +34,6 @@ pytestmark = pytest.mark.gpu
 
 def bits(a):
     return np.asarray(a, np.float64).view(np.int64)
-
-
-@contextlib.contextmanager
-def option(key, value):
-    v = ctypes.c_int64()
-    call("pamg_get_option", key.encode(), ctypes.byref(v))
-    call("pamg_set_option", key.encode(), int(value))
-    try:
-        yield
-    finally:
-        call("pamg_set_option", key.encode(), v.value)
 
 
 @pytest.fixture(scope="module")
