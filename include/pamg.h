@@ -316,7 +316,8 @@ int pamg_hier_profile_read(pamg_hier* H, double* ms_per_level_op /* nlevels*6 */
  * with HIP events on the launch stream. Op 6 is one Chebyshev step k >= 1 (SPEC §S9) of a square
  * operator: x is x_k, b the right-hand side, y the result, `omega` serves as both c1 and c2, and
  * x_{k-1} is a zeroed vector the call allocates beside b for its duration (the argument list has
- * no slot for it; the kernels stream it like any other). */
+ * no slot for it; the kernels stream it like any other). PAMG_E_STATE for op 3 on an operator
+ * in a symmetric layout (pamg_mat_layout out[9] bit 3), which has no prolongate-add kernel. */
 int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, const pamg_vec* b,
                      pamg_vec* y, double omega, int reps, double* avg_ms);
 

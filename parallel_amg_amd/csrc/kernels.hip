@@ -28,6 +28,7 @@
 // their numbers.
 
 #include "pamg_device.h"
+#include "div_rn.h"
 
 namespace pamg {
 namespace {
@@ -824,24 +825,8 @@ __device__ __forceinline__ void symtab_fill(SymTab<NU>& t, const double* __restr
     }
 }
 
-// RN(w / d) given r = RN(1 / d): q0 = RN(w r) and two residual corrections through exact FMA
-// residuals (Markstein: q1 is within one ulp of w / d, so q2 = RN(q1 + (w - q1 d) r) is the
-// correctly rounded quotient) — 5 f64 operations instead of the ~11 of the IEEE division
-// sequence. Outside |w| in [2^-900, 2^900] (zeros — whose sign the sequence could lose —,
-// subnormals, huge values, inf, NaN) and for a d whose reciprocal is not a normal number, the
-// division itself. Bitwise the same as w / d (checked on 3e8 random and near-midpoint cases,
-// tools/div_check.c, and by every oracle test of the kernels that use it).
-__device__ __forceinline__ double div_rn(double w, double d, double r) {
-    const double aw = fabs(w), ar = fabs(r);
-    if (aw >= 0x1p-900 && aw <= 0x1p900 && ar >= 0x1p-900 && ar <= 0x1p900) {
-        const double q0 = w * r;
-        const double e0 = __builtin_fma(-q0, d, w);
-        const double q1 = __builtin_fma(e0, r, q0);
-        const double e1 = __builtin_fma(-q1, d, w);
-        return __builtin_fma(e1, r, q1);
-    }
-    return w / d;
-}
+// div_rn(w, d, r = RN(1 / d)) = RN(w / d) in 5 f64 operations for |w|, |r| in [2^-500, 2^500],
+// the division itself elsewhere: div_rn.h (shared with tools/div_check.c, which checks it).
 
 __device__ __forceinline__ uint16_t tbd_pair_ids(const uint8_t* __restrict__ tid, int64_t j, int64_t n) {
     j = j < 0 ? 0 : (j > n - 2 ? n - 2 : j);  // (even j; clamped ones meet clear mask bits only)

@@ -4963,6 +4963,9 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
     }
     if (op >= 4 && !(A->interior.sym && (A->sym.tb_ok || A->sym.tb_part)))
         return fail(PAMG_E_STATE, "bench_rowop: op %d needs the temporally blocked layout (pamg_mat_layout bit 5)", op);
+    // (launch_sym has no prolongate-add: the layout is never built for a P; a launch would leave y as it was)
+    if (op == pamg::OP_PROLONG && (A->interior.sym || A->boundary.sym))
+        return fail(PAMG_E_STATE, "bench_rowop: the symmetric layouts have no prolongate-add kernel");
     if (x == y) return fail(PAMG_E_ARG, "bench_rowop: x and y must differ");
     CHECK(check_vec_for(A, x, "bench_rowop"));
     // a part's blocked passes (sweeps_part) feed each stage's output to the next stage's boundary
