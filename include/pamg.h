@@ -214,7 +214,8 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes);
  * column; then out[3] = the value table's entries, out[4] = the pattern count, out[8] = the kernel's
  * grid); bit 12: with bit 10, the rows hold 16-bit combination ids instead of 64-bit records
  * (pnc_compact; out[4] = the combinations); bit 13: with bit 9, one index byte per nonzero names an
- * (offset, value) pair of the group (ell_pair). */
+ * (offset, value) pair of the group (ell_pair); bit 14: with bit 10, the grid cuts into whole tiles
+ * and "pnc" = 1 launches the tiled march (k_rows_pnct) for it (out[8] is the grid of either march). */
 int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
 /* The windowed sliced-ELL layout of a matrix (ell_xwin; with pamg_mat_layout bits 9 and 13): out[0]
  * 1 where the matrix runs in it (else all 0), out[1] the groups whose x window is staged in LDS,
@@ -340,8 +341,9 @@ int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps
  * "sym_vd" (0 | 1: row-class dictionary of the symmetric layout), "ell" (0 | 1: sliced ELL for
  * large square operators with all own columns), "ell_restrict" (0 | 1: also restrictions, with
  * anchored offsets), "ell_min_rows" (rows from which ELL is taken), "ell_yblock" (0 | lines: the
- * blocked group order of a restriction over a grid), "pnc" (0 | 1: neighbour-coded
- * prolongations over a grid uploaded earlier on the context), "rpat" (0 | 1: pattern-dictionary
+ * blocked group order of a restriction over a grid), "pnc" (0 | 1 | 2: neighbour-coded
+ * prolongations over a grid uploaded earlier on the context; read per launch: 1 the tiled march where
+ * the plane cuts into 64 x 4 tiles, 2 always the line-block march; the same bits), "rpat" (0 | 1: pattern-dictionary
  * rows for restrictions whose rows repeat <= 255 patterns; tried before ELL), "pnc_compact" (0 | 1:
  * neighbour-coded rows as 16-bit ids of <= 1024 (pattern, values) combinations), "ell_pair" (0 | 1:
  * one ELL index byte per nonzero naming an (offset, value) pair where a group has <= 256), "ell_xwin"

@@ -222,7 +222,7 @@ def layout_of(M, part_set: int = 0) -> dict:
             "jr_fused": bool(out[9] & 32), "tm_vd": bool(out[9] & 64), "sym_vd": bool(out[9] & 128),
             "ell": bool(out[9] & 512), "pnc": bool(out[9] & 1024),
             "rpat": bool(out[9] & 2048), "pnc_compact": bool(out[9] & 4096),
-            "ell_pair": bool(out[9] & 8192)}  # (ell_xwin*: pamg_mat_ell_window)
+            "ell_pair": bool(out[9] & 8192), "pnc_tiled": bool(out[9] & 16384)}  # (ell_xwin*: pamg_mat_ell_window)
 
 
 def last_error() -> str:

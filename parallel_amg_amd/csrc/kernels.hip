@@ -2213,6 +2213,223 @@ __global__ __launch_bounds__(256) void k_rows_pnc(int nrows, int nx, int M, int 
     }
 }
 
+// a stream's march state in k_rows_pnct: the row's record, y / b / x, the anchors of the points
+// i - M, i, i + M, and (a tile's edge threads) the next plane's anchor of their ring point
+struct PnctRow {
+    uint2 rec;   // as PncRow::rec
+    double p0, p1;
+    int am, a0, ap;
+    int rg;
+};
+
+// k_rows_pnct: k_rows_pnc's z-march over a TX x TY tile of a plane instead of a 256-point piece of
+// a line (nx % TX == 0, ny % TY == 0; the same PncSet arrays, units, streams and unit order). A
+// lane loads one anchor per plane — its own point's, two planes ahead: the z neighbours' anchors
+// are the ones it holds — and the tile's edge threads one more, the ring point beside them (off the
+// grid: the edge row's own anchor; no code names such a point). A stream keeps the plane's anchors,
+// tile and ring, in LDS ((TX + 2) x (TY + 2) ints, two buffers: the next plane is written while
+// this one is read, one barrier per step), where the codes 1..4 read them. The gathers: a wave
+// takes the longest row of its lanes over the step's streams (Lmax; at the 512^3 P0 4.6 on
+// average, no row has 7) and one scalar switch picks the straight-line block that issues Lmax
+// gathers per stream (blocks for 3..7; a padded entry reloads the first entry's x, so the waits
+// count exactly). Only the gathers sit in the switch: the next planes' loads behind them and the
+// sums — over all 7 entries, the ones past the row's length selected away — follow it, which keeps
+// the kernel at k_rows_pnc's registers (whole step bodies in the switch: 86 VGPRs). Rows keep their
+// storage order and the left-to-right sum from +0.0 (SPEC S3): k_rows_pnc's bits.
+template <int OP, int NS, bool CP, int TX, int TY>
+__global__ __launch_bounds__(256) void k_rows_pnct(int nrows, int nx, int M, int nz, int zlen,
+                                                   const int* __restrict__ anc, const uint2* __restrict__ rec,
+                                                   const uint16_t* __restrict__ cid, const uint64_t* __restrict__ pvals,
+                                                   const uint32_t* __restrict__ ptab, int npat,
+                                                   const double* __restrict__ vtab, int nval,
+                                                   const double* __restrict__ x, const double* __restrict__ b,
+                                                   double* __restrict__ y, double omega) {
+    static_assert(TX * TY == 256 && 2 * TX + 2 * TY <= 256, "one row per lane; one ring point per edge thread");
+    constexpr int LW = TX + 2, LP = LW * (TY + 2);
+    __shared__ uint32_t lp[CP ? kPncCombMax : kPncPatMax];
+    __shared__ uint64_t lw[CP ? kPncCombMax : 1];
+    __shared__ double lv[kPncValMax];
+    __shared__ int la[NS][2][LP];
+    const int nxb = M >> 8;                                    // tiles of a plane
+    const int units = nxb * ((nz + zlen - 1) / zlen);
+    const int per = (units + 7) >> 3;
+    const int u = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);  // consecutive units on one XCD
+    if (u >= units) return;  // the whole workgroup, before the barrier
+    const int tid = (int)threadIdx.x;
+    for (int t = tid; t < npat; t += 256) lp[t] = ptab[t];
+    if constexpr (CP)
+        for (int t = tid; t < npat; t += 256) lw[t] = pvals[t];
+    for (int t = tid; t < nval; t += 256) lv[t] = vtab[t];
+    const int zc0 = (u / nxb) * zlen, zc1 = min(nz, zc0 + zlen);
+    const int part = (zc1 - zc0 + NS - 1) / NS;  // planes per stream
+    const int tpx = nx / TX, ny = M / nx, tb = u % nxb;
+    const int x0 = (tb % tpx) * TX, y0 = (tb / tpx) * TY;
+    const int ixy = (y0 + tid / TX) * nx + x0 + tid % TX;
+    const int lpos = (tid / TX + 1) * LW + tid % TX + 1;
+    // the ring: threads 0 .. 2 TX - 1 the lines below and above the tile, the last 2 TY threads the
+    // points left and right of it (rxy: the point in its plane, clamped to the tile's edge off the grid)
+    int rxy = -1, rpos = 0;
+    if (tid < TX) {
+        rxy = (y0 > 0 ? y0 - 1 : y0) * nx + x0 + tid;
+        rpos = tid + 1;
+    } else if (tid < 2 * TX) {
+        rxy = (y0 + TY < ny ? y0 + TY : y0 + TY - 1) * nx + x0 + tid - TX;
+        rpos = (TY + 1) * LW + tid - TX + 1;
+    } else if (tid >= 256 - TY) {
+        rxy = (y0 + tid - (256 - TY)) * nx + (x0 + TX < nx ? x0 + TX : x0 + TX - 1);
+        rpos = (tid - (256 - TY) + 1) * LW + TX + 1;
+    } else if (tid >= 256 - 2 * TY) {
+        rxy = (y0 + tid - (256 - 2 * TY)) * nx + (x0 > 0 ? x0 - 1 : x0);
+        rpos = (tid - (256 - 2 * TY) + 1) * LW;
+    }
+    int zs[NS], ze[NS], zl[NS], za[NS];
+    PnctRow r[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        zs[q] = zc0 + q * part;
+        ze[q] = min(zc1, zs[q] + part);
+        zl[q] = ze[q] > zs[q] ? ze[q] - 1 : zc1 - 1;  // a stream's last plane (an empty stream re-walks the chunk's)
+        // za: the plane of r.a0 — the row's plane until the stream's last, then on to the grid's last
+        // (steps that store nothing: any plane's anchors are columns)
+        const int z = za[q] = min(zs[q], zl[q]), zp = min(z + 1, nz - 1), i = z * M + ixy;
+        if constexpr (CP) r[q].rec = make_uint2((uint32_t)cid[i], 0u);
+        else r[q].rec = rec[i];
+        r[q].p0 = 0.0;
+        r[q].p1 = 0.0;
+        if constexpr (OP == OP_RESID || OP == OP_JACOBI) r[q].p0 = b[i];
+        if constexpr (OP == OP_PROLONG) r[q].p0 = y[i];
+        if constexpr (OP == OP_JACOBI) r[q].p1 = x[i];
+        r[q].a0 = anc[i];
+        r[q].am = anc[z > 0 ? i - M : i];
+        r[q].ap = anc[zp * M + ixy];
+        r[q].rg = 0;
+        la[q][0][lpos] = r[q].a0;
+        if (rxy >= 0) {
+            la[q][0][rpos] = anc[z * M + rxy];
+            r[q].rg = anc[zp * M + rxy];
+        }
+    }
+    __syncthreads();  // (the tables, the first planes' anchors)
+    for (int j = 0; j < part; ++j) {
+        uint32_t pw[NS];
+        int an[NS][4], lmax = 0;
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const uint32_t pid = CP ? r[q].rec.x : r[q].rec.x & 1023u;
+            pw[q] = pid < (uint32_t)npat ? lp[pid] : 0u;  // (kPncSkip / kPncCombSkip: no entries, no store)
+            lmax = max(lmax, (int)(pw[q] & 7u));
+            const int* pl = &la[q][j & 1][lpos];  // the anchors of i - 1, i + 1, i - nx, i + nx
+            an[q][0] = pl[-1];
+            an[q][1] = pl[1];
+            an[q][2] = pl[-LW];
+            an[q][3] = pl[LW];
+            // the next plane's anchors into the other buffer
+            la[q][(j & 1) ^ 1][lpos] = r[q].ap;
+            if (rxy >= 0) la[q][(j & 1) ^ 1][rpos] = r[q].rg;
+        }
+        // the gathers, LM per stream (col: -1 and x: 0.0 where none is issued — selected away in the sums)
+        int col[NS][kPncMaxLen];
+        double xv[NS][kPncMaxLen];
+        uint2 nrec[NS];
+        double np0[NS], np1[NS];
+        int ap2[NS], rg2[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q)
+#pragma unroll
+            for (int k = 0; k < kPncMaxLen; ++k) {
+                col[q][k] = -1;
+                xv[q][k] = 0.0;
+            }
+        auto loads = [&](auto lmc) {
+            constexpr int LM = decltype(lmc)::value;
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+                const int L = (int)(pw[q] & 7u);
+#pragma unroll
+                for (int k = 0; k < LM; ++k) {
+                    const uint32_t c = (pw[q] >> (3 + 3 * k)) & 7u;
+                    // codes 0 self, 1 i-1, 2 i+1, 3 i-nx, 4 i+nx, 5 i-M, 6 i+M: a select chain, no branches
+                    const int c01 = c & 1u ? an[q][0] : r[q].a0;
+                    const int c23 = c & 1u ? an[q][2] : an[q][1];
+                    const int c45 = c & 1u ? r[q].am : an[q][3];
+                    const int c03 = c & 2u ? c23 : c01;
+                    const int c47 = c & 2u ? r[q].ap : c45;
+                    col[q][k] = c & 4u ? c47 : c03;
+                    xv[q][k] = x[k < L ? col[q][k] : col[q][0]];
+                }
+            }
+        };
+        // the wave's longest row: uniform, so one scalar branch picks the block
+        const int lm = 3 + (__any(lmax > 3) ? 1 : 0) + (__any(lmax > 4) ? 1 : 0) + (__any(lmax > 5) ? 1 : 0) +
+                       (__any(lmax > 6) ? 1 : 0);
+        switch (lm) {
+            case 3: loads(std::integral_constant<int, 3>{}); break;
+            case 4: loads(std::integral_constant<int, 4>{}); break;
+            case 5: loads(std::integral_constant<int, 5>{}); break;
+            case 6: loads(std::integral_constant<int, 6>{}); break;
+            default: loads(std::integral_constant<int, 7>{}); break;
+        }
+        // under the gathers: the next planes (a stream's last plane reloads itself), the anchors two planes on
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const int in = min(zs[q] + j + 1, zl[q]) * M + ixy, z2 = min(za[q] + 2, nz - 1);
+            if constexpr (CP) nrec[q] = make_uint2((uint32_t)cid[in], 0u);
+            else nrec[q] = rec[in];
+            np0[q] = 0.0;
+            np1[q] = 0.0;
+            if constexpr (OP == OP_RESID || OP == OP_JACOBI) np0[q] = b[in];
+            if constexpr (OP == OP_PROLONG) np0[q] = y[in];
+            if constexpr (OP == OP_JACOBI) np1[q] = x[in];
+            ap2[q] = anc[z2 * M + ixy];
+            rg2[q] = 0;
+            if (rxy >= 0) rg2[q] = anc[z2 * M + rxy];
+        }
+        // the sums: an entry past the row's length (past the wave's longest: never loaded) is selected away
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const int i = min(zs[q] + j, zl[q]) * M + ixy, L = (int)(pw[q] & 7u);
+            // the value indices from bit 0 (compact: the combination's word; else the record's bits 10..)
+            uint64_t rr;
+            if constexpr (CP) rr = r[q].rec.x < (uint32_t)npat ? lw[r[q].rec.x] : 0ull;
+            else rr = (((uint64_t)r[q].rec.y << 32) | r[q].rec.x) >> 10;
+            double s = 0.0, dg = 0.0;
+#pragma unroll
+            for (int k = 0; k < kPncMaxLen; ++k) {
+                const bool ok = k < L;
+                const double v = lv[(uint32_t)(rr >> (7 * k)) & 127u];
+                const double p = v * xv[q][k];
+                const double t = s + p;
+                s = ok ? t : s;
+                if constexpr (OP == OP_JACOBI) dg = ok && col[q][k] == i ? v : dg;
+            }
+            double out;
+            if constexpr (OP == OP_SPMV) {
+                out = s;
+            } else if constexpr (OP == OP_RESID) {
+                out = r[q].p0 - s;
+            } else if constexpr (OP == OP_JACOBI) {
+                const double uu = r[q].p0 - s;
+                const double v = omega * uu;
+                const double w = v / dg;
+                out = r[q].p1 + w;
+            } else {
+                out = r[q].p0 + s;
+            }
+            const bool in = CP ? r[q].rec.x != (uint32_t)kPncCombSkip : (r[q].rec.x & 1023u) != (uint32_t)kPncSkip;
+            if (zs[q] + j < ze[q] && in) y[i] = out;
+            r[q].rec = nrec[q];
+            r[q].p0 = np0[q];
+            r[q].p1 = np1[q];
+            r[q].am = r[q].a0;
+            r[q].a0 = r[q].ap;
+            r[q].ap = ap2[q];
+            r[q].rg = rg2[q];
+            za[q] = min(za[q] + 1, nz - 1);
+        }
+        __syncthreads();  // (the next plane's anchors written, this plane's read)
+    }
+}
+
 template <int OP>
 __global__ __launch_bounds__(kBlock) void k_rows_long(
     const int* __restrict__ rows, const int* __restrict__ rowptr, const int* __restrict__ col,
@@ -2626,6 +2843,9 @@ void launch_sym(const pamg_mat& A, const double* x, const double* b, double* y, 
 // units and units sized to fill the chip in equal rounds 1.14 / 1.12 / 1.11 ms, against 1.09-1.10)
 constexpr int kPncZlen = 32, kPncStreams = 2;
 
+// Options::pnc read per launch: 1 the tiled march (k_rows_pnct) where the plane cuts into whole
+// kPncTx x kPncTy tiles, 2 (and the other grids) the line-block march (k_rows_pnc). Both take the
+// same units — 256 points of a plane over kPncZlen planes — and so the same grid (PncSet::grid).
 template <int OP>
 void launch_pnc(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s) {
     const PncSet& P = A.pnc;
@@ -2635,8 +2855,13 @@ void launch_pnc(const pamg_mat& A, const double* x, const double* b, double* y, 
         kern<<<(units + 7) / 8 * 8, 256, 0, s>>>((int)A.nrows, P.nx, P.nx * P.ny, P.nz, zlen, P.d_anc, P.d_rec, P.d_cid,
                                                 P.d_pvals, P.d_ptab, P.npat, P.d_vtab, P.nval, x, b, y, omega);
     };
-    if (P.d_cid) go(k_rows_pnc<OP, kPncStreams, true>);
-    else go(k_rows_pnc<OP, kPncStreams, false>);
+    if (options().pnc == 1 && pnc_tiled(P.nx, P.ny)) {
+        if (P.d_cid) go(k_rows_pnct<OP, kPncStreams, true, kPncTx, kPncTy>);
+        else go(k_rows_pnct<OP, kPncStreams, false, kPncTx, kPncTy>);
+    } else {
+        if (P.d_cid) go(k_rows_pnc<OP, kPncStreams, true>);
+        else go(k_rows_pnc<OP, kPncStreams, false>);
+    }
 }
 
 template <int OP>

@@ -1885,7 +1885,7 @@ int build_pnc(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
     }
     auto member = [&](int64_t i) { return in_set.empty() || in_set[i]; };
     const int64_t nx = grid[1], ny = grid[2], nz = grid[3], M = nx * ny;
-    if (n != nx * ny * nz || n <= 0 || M % 256 != 0) return PAMG_OK;  // (k_rows_pnc: 256-point blocks of a plane)
+    if (n != nx * ny * nz || n <= 0 || M % 256 != 0) return PAMG_OK;  // (k_rows_pnc / k_rows_pnct: 256-point blocks of a plane)
     std::vector<int> anc(n + kVecPad, 0);
     std::atomic<bool> ok{true};
     par_for(n, [&](int64_t a, int64_t b) {
@@ -2017,8 +2017,8 @@ int build_pnc(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
     P.nz = (int)nz;
     P.npat = (int)pats.size();
     P.nval = (int)vals.size();
-    // k_rows_pnc's grid (pamg_mat_layout out[8]): one workgroup per 256-point plane block and 32-plane
-    // chunk (kernels.hip launch_pnc)
+    // the grid of k_rows_pnct and k_rows_pnc (pamg_mat_layout out[8]): one workgroup per 256 points of a
+    // plane — a tile or a piece of a line — and 32-plane chunk (kernels.hip launch_pnc)
     {
         const int64_t zlen = std::min<int64_t>(32, nz);
         P.grid = (int)((M / 256 * ((nz + zlen - 1) / zlen) + 7) / 8 * 8);
@@ -2408,10 +2408,10 @@ int64_t pnc_bytes(const pamg_mat* A) {
 
 void pnc_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
     if (!t.pnc) return;
-    out[3] = A->pnc.nval;  // the pattern and value tables, k_rows_pnc's grid
+    out[3] = A->pnc.nval;  // the pattern and value tables, the grid of the march Options::pnc == 1 launches
     out[4] = A->pnc.npat;
     out[8] = A->pnc.grid;
-    out[9] |= 1024 | (A->pnc.d_cid ? 4096 : 0);
+    out[9] |= 1024 | (A->pnc.d_cid ? 4096 : 0) | (pamg::pnc_tiled(A->pnc.nx, A->pnc.ny) ? 16384 : 0);
 }
 
 void pnc_free(pamg::PncSet& P) {
@@ -4881,7 +4881,7 @@ const OptionRow kOptionTable[] = {
     {"tb_xfast", &O::tb_xfast, 0, 1, false},
     {"ell", &O::ell, 0, 1, false},
     {"ell_restrict", &O::ell_restrict, 0, 1, false},
-    {"pnc", &O::pnc, 0, 1, false},
+    {"pnc", &O::pnc, 0, 2, false},
     {"rpat", &O::rpat, 0, 1, false},
     {"pnc_compact", &O::pnc_compact, 0, 1, false},
     {"ell_pair", &O::ell_pair, 0, 1, false},
