@@ -150,6 +150,9 @@ int pamg_vec_download(pamg_ctx* ctx, const pamg_vec* v, double* own);
 int pamg_vec_download_ghosts(pamg_ctx* ctx, const pamg_vec* v, double* ghost);
 int pamg_vec_device_ptr(pamg_vec* v, double** dptr);                    /* zero-copy interop */
 int pamg_vec_fill(pamg_ctx* ctx, pamg_vec* v, double value);            /* fill!(v, a) */
+/* Own entry k becomes the SPEC §S2 generator value of global index i0 + k, computed on the device
+ * (the bits of pamg_gen_xstar(i0, n_own, seed)); ghost slots are untouched. i0 >= 0. */
+int pamg_vec_fill_xstar(pamg_ctx* ctx, pamg_vec* v, int64_t i0, uint64_t seed);
 int pamg_vec_copy(pamg_ctx* ctx, const pamg_vec* src, pamg_vec* dst);   /* copy!(dst, src) */
 int pamg_vec_axpby(pamg_ctx* ctx, double a, const pamg_vec* x, double b, pamg_vec* y); /* y=a x+b y */
 int pamg_vec_dot(pamg_ctx* ctx, const pamg_vec* x, const pamg_vec* y, double* out);    /* dot */
@@ -253,6 +256,16 @@ int pamg_chebyshev_coeffs(double lmax, double ratio, int degree, double* c1, dou
  * prolongation or restriction). */
 int pamg_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp1,
                    pamg_vec* tmp2, double lmax, double ratio, int degree);
+/* Power-iteration estimate of lambda_max(D^-1 A) from below (SPEC §S10). v holds the start vector
+ * (shaped as A's input, ghost slots included) and is overwritten with v^steps; y (A's output shape)
+ * with the last A v. Step k: y = A v (ghosts exchanged), lam[k-1] = sum v_i y_i / sum (a_ii v_i) v_i
+ * over the own rows, v_i = y_i / a_ii. all_parts = 1 sums over the ranks of the context (collective),
+ * 0 over this rank only (a level held whole on every rank). lam has `steps` entries, nondecreasing
+ * and <= lambda_max in exact arithmetic. PAMG_E_ARG for NULL arguments, v == y, steps outside
+ * 1..64, an operator that is not square or lacks a full diagonal, vectors that do not fit it, and
+ * a denominator that is zero or not finite. Runs eagerly (never graph-captured). */
+int pamg_estimate_lmax(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* v, pamg_vec* y, int steps,
+                       int all_parts, double* lam);
 
 /* ------------------------------------------------------------------ hierarchy / V-cycle */
 /* Levels 0..nlevels-1; P[l], R[l] for l < nlevels-1 (NULL entries otherwise). The coarsest
@@ -276,6 +289,10 @@ int pamg_hier_set_graph(pamg_hier* H, int enable);
 /* V(nu1, nu2): Jacobi sweeps before / after the coarse correction (SPEC §S6; default 1, 1;
  * 1..64). The first pre-sweep on levels >= 1 is the zero-guess form. */
 int pamg_hier_set_sweeps(pamg_hier* H, int nu1, int nu2);
+/* Replaces the Jacobi weights of levels 0 .. nlevels-2 (pamg_hier_create's omega; each finite and
+ * > 0, else PAMG_E_ARG) — e.g. 4 / (3 lmax_l) with an estimated bound (SPEC §S10). Changed weights
+ * drop the captured graphs; the temporally blocked passes and the pipeline keep qualifying. */
+int pamg_hier_set_omega(pamg_hier* H, const double* omega);
 /* The smoother of the V-cycle: PAMG_SMOOTHER_JACOBI (default; lmax and ratio ignored, lmax may be
  * NULL) or PAMG_SMOOTHER_CHEBYSHEV — one polynomial of degree nu1 before and one of degree nu2
  * after the coarse correction (the degrees are pamg_hier_set_sweeps'), level l over

@@ -24,6 +24,7 @@ using SparseArrays
 # that does `using PartitionedArrays, PamgHIP` calls them unqualified and unambiguously.
 export Context, ExchangePlan, DeviceVector, DeviceMatrix, HostCSR, VCycle, ExchangeTask, PamgError,
        download_own, download_ghosts, exchange_begin, residual!, jacobi!, jacobi_residual!, chebyshev!, chebyshev_coeffs, vcycle!, pcg!, set_sweeps!, set_smoother!,
+       fill_xstar!, estimate_lmax, set_omega!,
        set_perm!, setup_hierarchy, gen_grid, gen_xstar, read_mtx, rcm_order, locality_order, unique_id,
        comm_init!, runtime_versions, hip, World, world_spmv!, world_exchange!, world_dot, world_vcycle!,
        world_pcg!, world_abort!, world_reset!, world_broken, set_tag!
@@ -295,6 +296,9 @@ function device_pointer(v::DeviceVector)
 end
 Base.fill!(v::DeviceVector, a::Real) =
     (check(ccall((:pamg_vec_fill, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble), v.ctx.h, v.h, a)); v)
+"Own entry k = the SPEC §S2 generator value of global index i0 + k (0-based), computed on the device; ghost slots untouched."
+fill_xstar!(v::DeviceVector, i0::Integer, seed::Integer = 20240807) =
+    (check(ccall((:pamg_vec_fill_xstar, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt64), v.ctx.h, v.h, i0, seed)); v)
 Base.copy!(dst::DeviceVector, src::DeviceVector) =
     (check(ccall((:pamg_vec_copy, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), dst.ctx.h, src.h, dst.h)); dst)
 "y = a x + b y (own entries)."
@@ -451,6 +455,20 @@ chebyshev!(x::DeviceVector, A::DeviceMatrix, b::DeviceVector, tmp1::DeviceVector
     (check(ccall((:pamg_chebyshev, libpamg), Cint,
                  (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint),
                  A.ctx.h, A.h, x.h, b.h, tmp1.h, tmp2.h, lmax, ratio, degree)); x)
+"""
+    estimate_lmax(A, v, y; steps = 10, all_parts = true)
+
+`steps` power-iteration steps for λmax(D⁻¹A) from the start vector in `v` (SPEC §S10): returns
+λ₁ … λ_steps (nondecreasing, ≤ λmax); `v` becomes vᵐ, `y` the last A v. `all_parts`: sum over the
+ranks of the context (collective), or over this rank only for a level held whole on every rank.
+"""
+function estimate_lmax(A::DeviceMatrix, v::DeviceVector, y::DeviceVector; steps::Integer = 10, all_parts::Bool = true)
+    lam = zeros(Float64, max(steps, 1))
+    check(ccall((:pamg_estimate_lmax, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Float64}),
+                A.ctx.h, A.h, v.h, y.h, steps, all_parts ? 1 : 0, lam))
+    lam
+end
 "t = x + ω D⁻¹ (b - A x), r = b - A t (one fused pass where the matrix qualifies); returns whether it fused."
 function jacobi_residual!(t::DeviceVector, r::DeviceVector, A::DeviceMatrix, x::DeviceVector, b::DeviceVector, omega::Real)
     f = Ref{Cint}(0)
@@ -647,6 +665,14 @@ function set_smoother!(M::VCycle, kind::Symbol; ratio::Real = 4.0, lmax::Vector{
     k == 0 || length(lmax) >= nl || throw(DimensionMismatch("set_smoother!: lmax needs $nl entries"))
     check(ccall((:pamg_hier_set_smoother, libpamg), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cdouble), M.h, k,
                 k == 0 || nl == 0 ? Ptr{Float64}(C_NULL) : lmax, ratio))
+    M
+end
+"Replace the Jacobi weights of every level but the coarsest (e.g. 4 / (3 lmax_l) with an estimated bound, SPEC §S10)."
+function set_omega!(M::VCycle, omega::Vector{Float64})
+    nl = length(M.A) - 1
+    length(omega) >= nl || throw(DimensionMismatch("set_omega!: omega needs $nl entries"))
+    check(ccall((:pamg_hier_set_omega, libpamg), Cint, (Ptr{Cvoid}, Ptr{Float64}), M.h,
+                nl == 0 ? Ptr{Float64}(C_NULL) : omega))
     M
 end
 "Level-0 numbering of a hierarchy uploaded with locality permutations (1-based; nothing = none)."

@@ -69,6 +69,7 @@ SIGNATURES = {
     "pamg_vec_download_ghosts": [vp, vp, vp],
     "pamg_vec_device_ptr": [vp, pvp],
     "pamg_vec_fill": [vp, vp, dbl],
+    "pamg_vec_fill_xstar": [vp, vp, i64, C.c_uint64],
     "pamg_vec_copy": [vp, vp, vp],
     "pamg_vec_axpby": [vp, dbl, vp, dbl, vp],
     "pamg_vec_dot": [vp, vp, vp, pdbl],
@@ -89,6 +90,8 @@ SIGNATURES = {
     "pamg_jacobi_residual": [vp, vp, vp, vp, vp, vp, dbl, pi32],
     "pamg_chebyshev_coeffs": [dbl, dbl, i32, vp, vp],
     "pamg_chebyshev": [vp, vp, vp, vp, vp, vp, dbl, dbl, i32],
+    "pamg_estimate_lmax": [vp, vp, vp, vp, i32, i32, vp],
+    "pamg_hier_set_omega": [vp, vp],
     "pamg_hier_create": [vp, i32, vp, vp, vp, vp, i64, vp, i32, vp, pvp],
     "pamg_hier_destroy": [vp],
     "pamg_hier_set_graph": [vp, i32],

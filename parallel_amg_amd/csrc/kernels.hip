@@ -2627,6 +2627,45 @@ __global__ __launch_bounds__(kBlock) void k_dot_final(int np, const double* __re
     if (threadIdx.x == 0) *out = s;
 }
 
+// SPEC §S2 generator on the device (pamg_vec_fill_xstar): y[k] = x*_{i0 + k}. The integer hash, the
+// conversion of a 53-bit integer, the scaling by 2^-53 and 2u - 1 are all exact, so the bits are
+// pamg_gen_xstar's.
+__global__ void k_fill_xstar(int64_t n, int64_t i0, uint64_t seed, double* __restrict__ y) {
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t z = seed + (uint64_t)(i0 + k + 1) * 0x9E3779B97F4A7C15ULL;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        z = z ^ (z >> 31);
+        const double u = (double)(z >> 11) * (1.0 / 9007199254740992.0);
+        y[k] = 2.0 * u - 1.0;
+    }
+}
+
+// One step of the SPEC §S10 power iteration after y = A v: the partials of v.y and of (d v).v,
+// and v <- y / d, in one pass. Both sums walk k_dot_partial's grid-stride order and block_sum
+// tree on the same grid, so they are the bits of two launch_dot calls and the same run to run.
+__global__ __launch_bounds__(kBlock) void k_lmax_step(int64_t n, const double* __restrict__ y,
+                                                      const double* __restrict__ diag, double* __restrict__ v,
+                                                      double* __restrict__ pnum, double* __restrict__ pden) {
+    __shared__ double lds[2][kBlock / 64];
+    double a = 0.0, c = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kBlock) {
+        const double vi = v[i], yi = y[i], d = diag[i];
+        a += vi * yi;
+        const double dv = d * vi;
+        c += dv * vi;
+        v[i] = yi / d;
+    }
+    const double sa = block_sum(a, lds[0]);
+    const double sc = block_sum(c, lds[1]);
+    if (threadIdx.x == 0) {
+        pnum[blockIdx.x] = sa;
+        pden[blockIdx.x] = sc;
+    }
+}
+
 inline int grid_for(int64_t n, int cap = 8192) {
     int64_t g = (n + kBlock - 1) / kBlock;
     if (g < 1) g = 1;
@@ -3038,6 +3077,17 @@ void launch_cg_update(int64_t n, double alpha, const double* p, const double* q,
                       double* partials, int np, double* out, hipStream_t s) {
     k_cg_update<<<np, kBlock, 0, s>>>(n, alpha, p, q, x, r, partials);
     k_dot_final<<<1, kBlock, 0, s>>>(np, partials, out);
+}
+
+void launch_fill_xstar(int64_t n, int64_t i0, uint64_t seed, double* y, hipStream_t s) {
+    if (n > 0) k_fill_xstar<<<grid_for(n), kBlock, 0, s>>>(n, i0, seed, y);
+}
+
+void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v, double* partials, int np,
+                      double* out, hipStream_t s) {
+    k_lmax_step<<<np, kBlock, 0, s>>>(n, y, diag, v, partials, partials + np);
+    k_dot_final<<<1, kBlock, 0, s>>>(np, partials, out);
+    k_dot_final<<<1, kBlock, 0, s>>>(np, partials + np, out + 1);
 }
 
 }  // namespace pamg

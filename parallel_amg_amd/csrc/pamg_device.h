@@ -469,5 +469,11 @@ int dot_partials(int64_t n);
 // x += alpha p; r -= alpha q; out = r.r (bit-identical to two launch_axpby + launch_dot)
 void launch_cg_update(int64_t n, double alpha, const double* p, const double* q, double* x, double* r,
                       double* partials, int np, double* out, hipStream_t s);
+// y[k] = the SPEC §S2 generator value of index i0 + k (the bits of pamg_gen_xstar)
+void launch_fill_xstar(int64_t n, int64_t i0, uint64_t seed, double* y, hipStream_t s);
+// SPEC §S10 step after y = A v: out[0] = v.y, out[1] = (diag v).v (each with launch_dot's bits),
+// v <- y / diag. partials holds 2 np doubles, np = dot_partials(n).
+void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v, double* partials, int np,
+                      double* out, hipStream_t s);
 
 }  // namespace pamg

@@ -3036,6 +3036,38 @@ int reduce_scalar(pamg_ctx* ctx, int64_t n, const double* x, const double* y, do
     });
 }
 
+// The two sums of a SPEC §S10 step after y = A v, with v <- y / diag in the same pass:
+// out[0] = sum v_i y_i, out[1] = sum (a_ii v_i) v_i over the own rows — of every rank when
+// all_parts (the cross-rank sums of reduce_with), else of this rank alone (a level held whole).
+int lmax_sums(pamg_ctx* ctx, int64_t n, const double* y, const double* diag, double* v, bool all_parts,
+              double out[2]) {
+    hipStream_t s = ctx->s_comp;
+    const int np = pamg::dot_partials(n);
+    if (2 * np + 2 > ctx->red_cap) return fail(PAMG_E_STATE, "reduction workspace too small");
+    double* res = ctx->d_red + ctx->red_cap - 2;
+    pamg::launch_lmax_step(n, y, diag, v, ctx->d_red, np, res, s);
+    HIPC(hipGetLastError());
+    const bool cross = all_parts && ctx->nranks > 1;
+    if (cross && ctx->comm) NCCLC(ncclAllReduce(res, res, 2, ncclDouble, ncclSum, ctx->comm, s));
+    HIPC(hipMemcpyAsync(ctx->h_red, res, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    out[0] = ctx->h_red[0];
+    out[1] = ctx->h_red[1];
+    if (cross && ctx->world) {
+        CHECK(allreduce_local(ctx, &out[0]));
+        CHECK(allreduce_local(ctx, &out[1]));
+    }
+    if (cross && ctx->host_fn) {
+        const int64_t two = 2;
+        double sum[2] = {0.0, 0.0};
+        if (ctx->host_fn(ctx->host_user, 2, 1, nullptr, &two, out, &two, sum) != 0)
+            return fail(PAMG_E_RCCL, "allreduce: host transport failed");
+        out[0] = sum[0];
+        out[1] = sum[1];
+    }
+    return PAMG_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ hierarchy type
@@ -3332,9 +3364,9 @@ int pamg_ctx_create(int device, pamg_ctx** out) {
     HIPC(hipStreamCreateWithFlags(&c->s_comm, hipStreamNonBlocking));
     HIPC(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     HIPC(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    c->red_cap = 2048;
+    c->red_cap = 2 * 1024 + 2;  // two sets of dot_partials' 1024 partials + two results (lmax_sums)
     CHECK(dalloc(&c->d_red, c->red_cap));
-    HIPC(hipHostMalloc(reinterpret_cast<void**>(&c->h_red), sizeof(double)));
+    HIPC(hipHostMalloc(reinterpret_cast<void**>(&c->h_red), 2 * sizeof(double)));
     *out = c.release();
     return PAMG_OK;
 }
@@ -3777,6 +3809,15 @@ int pamg_vec_fill(pamg_ctx* ctx, pamg_vec* v, double value) {
     if (!ctx || !v) return fail(PAMG_E_ARG, "vec_fill: bad args");
     CHECK(set_device(ctx));
     pamg::launch_fill(v->n_own, value, v->d, ctx->s_comp);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_vec_fill_xstar(pamg_ctx* ctx, pamg_vec* v, int64_t i0, uint64_t seed) {
+    if (!ctx || !v || i0 < 0) return fail(PAMG_E_ARG, "vec_fill_xstar: bad args");
+    CHECK(set_device(ctx));
+    pamg::launch_fill_xstar(v->n_own, i0, seed, v->d, ctx->s_comp);
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(ctx->s_comp));
     return PAMG_OK;
@@ -4409,6 +4450,25 @@ int pamg_hier_set_sweeps(pamg_hier* H, int nu1, int nu2) {
     return PAMG_OK;
 }
 
+int pamg_hier_set_omega(pamg_hier* H, const double* omega) {
+    if (!H) return fail(PAMG_E_ARG, "hier_set_omega: NULL");
+    const int nl = H->L - 1;
+    if (nl > 0 && !omega) return fail(PAMG_E_ARG, "hier_set_omega: omega is NULL");
+    bool same = true;
+    for (int l = 0; l < nl; ++l) {
+        if (!(omega[l] > 0.0) || !std::isfinite(omega[l]))
+            return fail(PAMG_E_ARG, "hier_set_omega: omega[%d] must be finite and > 0", l);
+        same = same && omega[l] == H->omega[l];
+    }
+    if (!same) {
+        (void)hipSetDevice(H->ctx->device);
+        (void)hipStreamSynchronize(H->ctx->s_comp);
+        drop_graph(H);  // the captured cycles carry the old weights as launch arguments
+    }
+    std::copy(omega, omega + nl, H->omega.begin());
+    return PAMG_OK;
+}
+
 int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ratio) {
     if (!H || (kind != PAMG_SMOOTHER_JACOBI && kind != PAMG_SMOOTHER_CHEBYSHEV))
         return fail(PAMG_E_ARG, "hier_set_smoother: bad hierarchy or smoother kind");
@@ -4472,6 +4532,30 @@ int pamg_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec
     if (res != x->d)
         HIPC(hipMemcpyAsync(x->d, res, sizeof(double) * x->n_own, hipMemcpyDeviceToDevice, ctx->s_comp));
     HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_estimate_lmax(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* v, pamg_vec* y, int steps, int all_parts,
+                       double* lam) {
+    if (!ctx || !A || !v || !y || !lam) return fail(PAMG_E_ARG, "estimate_lmax: NULL");
+    if (v == y) return fail(PAMG_E_ARG, "estimate_lmax: v and y must differ");
+    if (steps < 1 || steps > 64) return fail(PAMG_E_ARG, "estimate_lmax: need 1 <= steps <= 64");
+    if (A->nrows != (A->plan ? A->plan->n_own : A->ncols) || A->interior.pnc || A->interior.rpat)
+        return fail(PAMG_E_ARG, "estimate_lmax: the operator must be square (%lld rows, %lld own columns)",
+                    (long long)A->nrows, (long long)(A->plan ? A->plan->n_own : A->ncols));
+    if (!A->d_diag && A->nrows > 0) return fail(PAMG_E_ARG, "estimate_lmax: matrix lacks a nonzero diagonal");
+    CHECK(check_vec_for(A, v, "estimate_lmax"));
+    if (y->n_own != A->nrows) return fail(PAMG_E_ARG, "estimate_lmax: output size mismatch");
+    CHECK(set_device(ctx));
+    for (int k = 0; k < steps; ++k) {
+        CHECK(apply(ctx, A, pamg::OP_SPMV, v->d, nullptr, y->d, 0.0));
+        double sums[2] = {0.0, 0.0};
+        CHECK(lmax_sums(ctx, A->nrows, y->d, A->d_diag, v->d, all_parts != 0, sums));
+        if (sums[1] == 0.0 || !std::isfinite(sums[1]))
+            return fail(PAMG_E_ARG, "estimate_lmax: step %d: sum (a_ii v_i) v_i = %g (a zero or non-finite iterate)",
+                        k + 1, sums[1]);
+        lam[k] = sums[0] / sums[1];
+    }
     return PAMG_OK;
 }
 

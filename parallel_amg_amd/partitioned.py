@@ -322,6 +322,11 @@ class PVector:
     def fill(self, v: float):
         call("pamg_vec_fill", self.ctx.handle, self._h, float(v))
 
+    def fill_xstar(self, i0: int, seed: int):
+        """Own entry k = the SPEC §S2 generator value of global index i0 + k, computed on the device
+        (the bits of ``hcsr.gen_xstar(i0, n_own, seed)``); ghost slots are untouched."""
+        call("pamg_vec_fill_xstar", self.ctx.handle, self._h, int(i0), int(seed))
+
     def __del__(self):
         _release(self, "pamg_vec_destroy")
 
@@ -412,6 +417,15 @@ def chebyshev(x: PVector, A: PSparseMatrix, b: PVector, tmp1: PVector, tmp2: PVe
     call("pamg_chebyshev", A.ctx.handle, A.handle, x.handle, b.handle, tmp1.handle, tmp2.handle, float(lmax),
          float(ratio), int(degree))
     return x
+
+
+def estimate_lmax(A: PSparseMatrix, v: PVector, y: PVector, steps: int = 10, all_parts: bool = True) -> np.ndarray:
+    """``steps`` power-iteration steps for lambda_max(D^-1 A) from the start vector in v (SPEC §S10):
+    returns lambda_1 .. lambda_steps; v becomes v^steps, y the last A v. ``all_parts``: sum over the
+    parts of the context (collective), or over this part only for a level held whole on every part."""
+    lam = np.zeros(max(int(steps), 1))
+    call("pamg_estimate_lmax", A.ctx.handle, A.handle, v.handle, y.handle, int(steps), int(bool(all_parts)), ptr(lam))
+    return lam
 
 
 def jacobi_residual(t: PVector, r: PVector, A: PSparseMatrix, x: PVector, b: PVector, omega: float) -> bool:

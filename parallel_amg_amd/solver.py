@@ -11,8 +11,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import call, ptr
-from .hierarchy import HostHierarchy
-from .partitioned import Context, PSparseMatrix, PVector, _release
+from .hcsr import gen_xstar
+from .hierarchy import SEED, HostHierarchy
+from .partitioned import Context, PSparseMatrix, PVector, _release, estimate_lmax
 
 OPS = ("jacobi_pre", "residual", "restrict", "prolong", "jacobi_post", "coarse")
 
@@ -158,16 +159,59 @@ class AMGSolver:
         """V(nu1, nu2) weighted-Jacobi sweeps (SPEC §S6; default V(1, 1))."""
         call("pamg_hier_set_sweeps", self._h, int(nu1), int(nu2))
 
-    def set_smoother(self, kind: str = "jacobi", ratio: float = 4.0):
+    def estimate_lmax(self, steps: int = 10, boost: float = 1.1, seed: int = SEED):
+        """Device estimate of lambda_max(D^-1 A_l) for every level but the coarsest (SPEC §S10):
+        ``steps`` power-iteration steps from the §S2 generator vector of seed ``seed + l`` (global
+        row numbering), then lmax_l = min(rho_l, boost * lambda_steps). Returns the L-1 values and
+        keeps the raw lambda histories in ``self.lmax_hist``. Collective on several parts: every
+        part calls it, and every part gets the same values."""
+        out, self.lmax_hist = [], []
+        for l in range(self.L - 1):
+            A, lp = self.A_dev[l], self._H.levels[l][self.part]
+            whole = l >= self.rep_level
+            i0 = 0 if whole else int(lp.offsets[self.part])
+            v, y = A.new_input_vector(), A.new_output_vector()
+            if self.perm[l] is None:
+                v.fill_xstar(i0, seed + l)
+            else:  # device row i is host row perm[i]: the generator values in the device numbering
+                v.set(gen_xstar(i0, A.nrows, seed + l)[self.perm[l]])
+            lam = estimate_lmax(A, v, y, steps, all_parts=not whole)
+            self.lmax_hist.append(lam)
+            out.append(min(lp.rho, boost * float(lam[-1])))
+        return out
+
+    def set_smoother(self, kind: str = "jacobi", ratio: float = 4.0, lmax="gershgorin"):
         """The V-cycle's smoother: "jacobi" (default) or "chebyshev" — one polynomial of degree nu1
         before and nu2 after the coarse correction (``set_sweeps`` gives the degrees), level l over
-        [rho_l / ratio, rho_l] with the setup's bound rho_l (``LevelPart.rho``; SPEC §S9)."""
+        [lmax_l / ratio, lmax_l] (SPEC §S9). ``lmax``: "gershgorin" (the setup's bound rho_l,
+        ``LevelPart.rho``), "estimate" (``estimate_lmax()`` with its defaults, SPEC §S10) or a
+        sequence of L-1 floats. For Jacobi a non-default ``lmax`` sets the weights
+        omega_l = 4 / (3 lmax_l) (pamg_hier_set_omega); "gershgorin" restores the setup's."""
         kinds = {"jacobi": 0, "chebyshev": 1}
         if kind not in kinds:
             raise ValueError(f"unknown smoother {kind!r} (jacobi | chebyshev)")
-        lmax = np.asarray([self._H.levels[l][self.part].rho for l in range(self.L - 1)], np.float64)
-        call("pamg_hier_set_smoother", self._h, kinds[kind], ptr(lmax) if kinds[kind] else None, float(ratio))
+        nl = self.L - 1
+        if isinstance(lmax, str):
+            if lmax not in ("gershgorin", "estimate"):
+                raise ValueError(f"unknown lmax {lmax!r} (gershgorin | estimate | a sequence of {nl} floats)")
+            bound = self.estimate_lmax() if lmax == "estimate" else None
+        else:
+            bound = [float(v) for v in lmax]
+            if len(bound) != nl:
+                raise ValueError(f"lmax needs {nl} entries, got {len(bound)}")
+        # the Jacobi weights: 4 / (3 lmax_l) (the expression of SPEC §S4.1) for Jacobi with a bound
+        # of its own, else the setup's — so "jacobi" without lmax is the setup's cycle again
+        if bound is not None and kind == "jacobi":
+            omega = [4.0 / (3.0 * v) for v in bound]
+        else:
+            omega = [float(w) for w in self.omega[:nl]]
+        if bound is None:
+            bound = [self._H.levels[l][self.part].rho for l in range(nl)]
+        lm, om = np.asarray(bound, np.float64), np.asarray(omega, np.float64)
+        call("pamg_hier_set_smoother", self._h, kinds[kind], ptr(lm) if kinds[kind] else None, float(ratio))
+        call("pamg_hier_set_omega", self._h, ptr(om))
         self.smoother = kind
+        self.lmax = list(bound)
 
     def graph_state(self) -> dict:
         e, c, f = C.c_int(), C.c_int(), C.c_int()

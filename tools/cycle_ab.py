@@ -9,8 +9,11 @@ switch) and checked for the same bits of x.
 --pcg compares smoothers instead, on the same upload: each variant — j or c (Jacobi, Chebyshev with
 --ratio) followed by the two sweep counts / degrees — solves A x = b by PCG to --rtol once to warm up
 (and capture) and --rounds times timed; one JSON line per solve with its time and iteration count.
+A trailing e (j11e, c22e) runs the variant over the estimated bounds of SPEC §S10 (AMGSolver.estimate_lmax,
+10 steps, boost 1.1; estimated once, its wall time per level on a line of its own) instead of Gershgorin's.
 
     python tools/cycle_ab.py --pcg j11,j22,j33,c22,c33 --rounds 3 > pcg.jsonl
+    python tools/cycle_ab.py --pcg j11,j11e,c22,c22e --rounds 3 > pcg_estimate.jsonl
 """
 from __future__ import annotations
 
@@ -34,6 +37,27 @@ from parallel_amg_amd.solver import AMGSolver  # noqa: E402
 
 def set_opt(k, v):
     _lib.call("pamg_set_option", k.encode(), int(v))
+
+
+def estimate_timed(ctx, S, a):
+    """S.estimate_lmax() with its defaults; prints the bounds beside Gershgorin's and, from a second
+    pass of the same calls one level at a time, the wall time of each level's estimate."""
+    from parallel_amg_amd.partitioned import estimate_lmax
+    from parallel_amg_amd.hierarchy import SEED
+    est = S.estimate_lmax()
+    ms = []
+    for l in range(S.L - 1):
+        A = S.A_dev[l]
+        v, y = A.new_input_vector(), A.new_output_vector()
+        ctx.sync()
+        ts = time.perf_counter()
+        v.fill_xstar(0, SEED + l)
+        estimate_lmax(A, v, y, 10)
+        ms.append(round((time.perf_counter() - ts) * 1e3, 3))
+    print(json.dumps({"kind": a.kind, "n": a.n, "estimate_lmax": est, "lambda_10": [float(h[-1]) for h in S.lmax_hist],
+                      "gershgorin": [S._H.levels[l][S.part].rho for l in range(S.L - 1)],
+                      "rows": S.level_rows[:-1], "estimate_ms_per_level": ms}), flush=True)
+    return est
 
 
 def main():
@@ -62,8 +86,14 @@ def main():
     mul(b, Af, PVector(ctx, Af.n_own_cols, Af.n_ghost, xs[0]))
     print(f"# setup + upload {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
     if a.pcg:
+        est = None
         for var in a.pcg.split(","):
-            S.set_smoother({"j": "jacobi", "c": "chebyshev"}[var[0]], ratio=a.ratio)
+            if len(var) not in (3, 4) or var[0] not in "jc" or var[3:] not in ("", "e"):
+                ap.error(f"bad --pcg variant {var!r}")
+            if var.endswith("e") and est is None:
+                est = estimate_timed(ctx, S, a)
+            S.set_smoother({"j": "jacobi", "c": "chebyshev"}[var[0]], ratio=a.ratio,
+                           lmax=est if var.endswith("e") else "gershgorin")
             S.set_sweeps(int(var[1]), int(var[2]))
             for r in range(-1, a.rounds):  # (-1: warm-up and graph capture)
                 x = S.new_vector()
