@@ -363,7 +363,7 @@ struct pamg_ctx {
     double* d_red = nullptr;  // reduction workspace (partials + result)
     int red_cap = 0;
     double* h_red = nullptr;  // pinned host scalar
-    // upload staging (runtime.hip h2d): two pinned 64 MiB buffers and their DMA-done events,
+    // upload staging (matrix.hip h2d): two pinned 64 MiB buffers and their DMA-done events,
     // created on first use on this context's device and owned by the context
     char* stage[2] = {nullptr, nullptr};
     hipEvent_t stage_done[2] = {nullptr, nullptr};

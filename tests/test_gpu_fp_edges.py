@@ -236,7 +236,7 @@ def case_tall(ctx, name):
 
 def case_long(ctx):
     """k_rows_long: rows of 5000 and 9000 nonzeros, more than any tile holds (the upload gives such a
-    row a workgroup of its own, runtime.hip tiles_build), beside rows of 2047 .. 2049, 1 and 0."""
+    row a workgroup of its own, matrix.hip build_tiles), beside rows of 2047 .. 2049, 1 and 0."""
     lengths = LENGTHS["long"]
     M = host("long", lambda: random_csr(np.random.default_rng(11), lengths, max(lengths) + 1))
     D = upload(ctx, M)

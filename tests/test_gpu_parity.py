@@ -1458,7 +1458,7 @@ def test_sym_dia_vcycle_same_bits_either_layout(ctx):
 def test_tile_major_value_dictionary_bit_exact(ctx, npal, tnnz, lengths):
     """8-bit per-tile value dictionaries in tile-major slots (value_dict, where the 4-bit ones do
     not fit and every tile has <= 256 distinct values — the 512^3 level-1 operator's case): SpMV,
-    residual, Jacobi and prolongate-add bit-exact with the oracle. The rule (runtime.hip
+    residual, Jacobi and prolongate-add bit-exact with the oracle. The rule (matrix.hip
     build_tile_major): the set takes them when its widest tile has 17..256 distinct values
     (bit patterns), <= 128 on 2048-nonzero tiles (the kernel's LDS table), rounded up to 4.
     Every value here (the diagonal too) is a palette value, and each tile draws ~2000 of them,
