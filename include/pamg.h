@@ -322,6 +322,25 @@ int pamg_vcycle_async(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* 
  * res_hist (maxit + 1 entries, may be NULL) gets ||r_0||, ||r_1||, ... */
 int pamg_pcg(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* b, double rtol,
              int maxit, int* iters, double* res_hist);
+/* pamg_pcg with alpha, beta, rho and r.r kept in device memory and the iteration replayed as two
+ * captured graphs (SPEC §S11): same recurrence, and x, *iters and res_hist carry pamg_pcg's bits
+ * for every lookahead. The host waits once for ||r_0||, then
+ *   lookahead = 0: once per iteration (pamg_pcg waits three times), for the convergence check,
+ *     before the preconditioner of that iteration is enqueued; nothing runs past convergence;
+ *   lookahead = L >= 1: never in steady state — iteration j is enqueued whole and only the
+ *     recorded outcome of iteration j - L is waited for, so the stream stays fed, and up to L
+ *     iterations (one SpMV and one V-cycle each, their vector updates switched off on the device)
+ *     run after convergence.
+ * So L >= 1 pays where an iteration is short next to a host round trip, and L = 0 where a V-cycle
+ * costs more than the waits it hides ("Device-resident PCG"). stats (may be NULL):
+ * {iterations enqueued, of those after convergence}. One part only: PAMG_E_STATE on a context
+ * with nranks > 1, before anything is launched or exchanged. */
+int pamg_pcg_resident(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* b, double rtol, int maxit,
+                      int lookahead, int* iters, double* res_hist, int stats[2]);
+/* The stopping bound of pamg_pcg_resident (host arithmetic, no device needed): *out = the largest
+ * double c whose correctly rounded square root is <= thr, so that rr <= c is the test
+ * sqrt(rr) <= thr. thr >= 0 (else PAMG_E_ARG); 0 -> 0, +inf -> +inf. */
+int pamg_pcg_rr_threshold(double thr, double* out);
 /* Kernel timing of the last pamg_vcycle/_async (events on the compute stream): per level,
  * milliseconds spent in [jacobi_pre, residual, restrict, prolong, jacobi_post, coarse]. */
 int pamg_hier_profile(pamg_hier* H, int enable);

@@ -706,14 +706,36 @@ function LinearAlgebra.ldiv!(x::DeviceVector, M::VCycle, b::DeviceVector)
                 M.ctx.h, M.h, x.h, b.h, M.ncycles, C_NULL))
     x
 end
-"CG preconditioned by one V-cycle (SPEC §S8), entirely on the device; returns (iterations, ‖r_k‖ history)."
-function pcg!(x::DeviceVector, M::VCycle, b::DeviceVector; rtol::Real = 1e-8, maxit::Integer = 100)
+"""
+    pcg!(x, M, b; rtol = 1e-8, maxit = 100, lookahead = nothing)
+
+CG preconditioned by one V-cycle (SPEC §S8), entirely on the device; returns (iterations, ‖r_k‖ history).
+`lookahead = nothing` is `pamg_pcg` (scalars on the host, three waits per iteration). An integer takes
+`pamg_pcg_resident` (SPEC §S11, one part only; same bits): `0` waits once per iteration, `L ≥ 1` only for
+the outcome of iteration j − L, at the price of up to L iterations run past convergence; the third value
+returned is then (iterations enqueued, of those after convergence).
+"""
+function pcg!(x::DeviceVector, M::VCycle, b::DeviceVector; rtol::Real = 1e-8, maxit::Integer = 100,
+              lookahead::Union{Nothing,Integer} = nothing)
     hist = zeros(maxit + 1)
     it = Ref{Cint}(0)
-    check(ccall((:pamg_pcg, libpamg), Cint,
-                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cint}, Ptr{Float64}),
-                M.ctx.h, M.h, x.h, b.h, rtol, maxit, it, hist))
-    (Int(it[]), hist[1:it[]+1])
+    if lookahead === nothing
+        check(ccall((:pamg_pcg, libpamg), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cint}, Ptr{Float64}),
+                    M.ctx.h, M.h, x.h, b.h, rtol, maxit, it, hist))
+        return (Int(it[]), hist[1:it[]+1])
+    end
+    stats = zeros(Cint, 2)
+    check(ccall((:pamg_pcg_resident, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Cint, Ptr{Cint}, Ptr{Float64}, Ptr{Cint}),
+                M.ctx.h, M.h, x.h, b.h, rtol, maxit, lookahead, it, hist, stats))
+    (Int(it[]), hist[1:it[]+1], (Int(stats[1]), Int(stats[2])))
+end
+"The stopping bound of `pamg_pcg_resident`: the largest Float64 whose correctly rounded square root is ≤ thr."
+function pcg_rr_threshold(thr::Real)
+    out = Ref{Cdouble}(0.0)
+    check(ccall((:pamg_pcg_rr_threshold, libpamg), Cint, (Cdouble, Ptr{Cdouble}), thr, out))
+    out[]
 end
 
 """

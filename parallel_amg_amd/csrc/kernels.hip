@@ -2956,6 +2956,92 @@ void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const
         k_rows_long<OP><<<ts.n_long, kBlock, 0, s>>>(ts.d_long, A.d_rowptr, A.d_col, A.d_val, x,
                                                      b, y, omega, ch.c1, ch.xold);
 }
+
+// ------------------------------------------------------------------ device-resident PCG (SPEC §S11)
+// The scalar steps of pamg_pcg_resident: alpha, beta, rho and r.r live in a PcgScalars block, the
+// kernels read them from there, and the sums are k_dot_final's (same stride, same block_sum tree
+// over the partials of k_dot_partial / k_cg_update's grid), so every value carries pamg_pcg's bits.
+// Each kernel returns at once when S->done is set (read before any barrier, the same in every
+// thread): an iteration enqueued past convergence changes nothing these kernels own.
+
+// alpha = rz / (p, q) from the partials of k_dot_partial(p, q)
+__global__ __launch_bounds__(kBlock) void k_pcg_alpha(int np, const double* __restrict__ partials, PcgScalars* S) {
+    if (S->done) return;
+    __shared__ double lds[kBlock / 64];
+    double v = 0.0;
+    for (int i = threadIdx.x; i < np; i += kBlock) v += partials[i];
+    const double s = block_sum(v, lds);
+    if (threadIdx.x == 0) {
+        S->pq = s;
+        S->alpha = S->rz / s;
+    }
+}
+
+// k_cg_update with alpha loaded from S
+__global__ __launch_bounds__(kBlock) void k_pcg_update(int64_t n, const PcgScalars* S, const double* __restrict__ p,
+                                                       const double* __restrict__ q, double* __restrict__ x,
+                                                       double* __restrict__ r, double* __restrict__ partials) {
+    if (S->done) return;
+    __shared__ double lds[kBlock / 64];
+    const double alpha = S->alpha;
+    const double na = -alpha;
+    double v = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kBlock) {
+        const double u = alpha * p[i];
+        const double w = 1.0 * x[i];
+        x[i] = u + w;
+        const double u2 = na * q[i];
+        const double w2 = 1.0 * r[i];
+        const double rn = u2 + w2;
+        r[i] = rn;
+        v += rn * rn;
+    }
+    const double s = block_sum(v, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// rr_k = r.r from k_pcg_update's partials, recorded; done = (rr_k <= rr_max), false for a NaN
+__global__ __launch_bounds__(kBlock) void k_pcg_check(int np, const double* __restrict__ partials, PcgScalars* S,
+                                                      double* __restrict__ rr_hist) {
+    if (S->done) return;
+    __shared__ double lds[kBlock / 64];
+    double v = 0.0;
+    for (int i = threadIdx.x; i < np; i += kBlock) v += partials[i];
+    const double s = block_sum(v, lds);
+    if (threadIdx.x == 0) {
+        const int k = S->k + 1;
+        S->rr = s;
+        S->k = k;
+        rr_hist[k] = s;
+        S->done = s <= S->rr_max ? 1 : 0;
+    }
+}
+
+// beta = (r, z) / rz, rz = (r, z) from the partials of k_dot_partial(r, z)
+__global__ __launch_bounds__(kBlock) void k_pcg_beta(int np, const double* __restrict__ partials, PcgScalars* S) {
+    if (S->done) return;
+    __shared__ double lds[kBlock / 64];
+    double v = 0.0;
+    for (int i = threadIdx.x; i < np; i += kBlock) v += partials[i];
+    const double s = block_sum(v, lds);
+    if (threadIdx.x == 0) {
+        S->beta = s / S->rz;
+        S->rz = s;
+    }
+}
+
+// p = 1.0 z + beta p: k_axpby with bb loaded from S
+__global__ void k_pcg_dir(int64_t n, const PcgScalars* S, const double* __restrict__ z, double* __restrict__ p) {
+    if (S->done) return;
+    const double bb = S->beta;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const double u = 1.0 * z[i];
+        const double v = bb * p[i];
+        p[i] = u + v;
+    }
+}
 }  // namespace
 
 void launch_sym_tb(const pamg_mat& A, const TbArgs& ta, hipStream_t s) {
@@ -3088,6 +3174,21 @@ void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v,
     k_lmax_step<<<np, kBlock, 0, s>>>(n, y, diag, v, partials, partials + np);
     k_dot_final<<<1, kBlock, 0, s>>>(np, partials, out);
     k_dot_final<<<1, kBlock, 0, s>>>(np, partials + np, out + 1);
+}
+
+void launch_pcg_half_a(int64_t n, PcgScalars* S, const double* p, const double* q, double* x, double* r,
+                       double* partials, int np, double* rr_hist, hipStream_t s) {
+    k_dot_partial<<<np, kBlock, 0, s>>>(n, p, q, partials);
+    k_pcg_alpha<<<1, kBlock, 0, s>>>(np, partials, S);
+    k_pcg_update<<<np, kBlock, 0, s>>>(n, S, p, q, x, r, partials);
+    k_pcg_check<<<1, kBlock, 0, s>>>(np, partials, S, rr_hist);
+}
+
+void launch_pcg_half_b(int64_t n, PcgScalars* S, const double* r, const double* z, double* p, double* partials,
+                       int np, hipStream_t s) {
+    k_dot_partial<<<np, kBlock, 0, s>>>(n, r, z, partials);
+    k_pcg_beta<<<1, kBlock, 0, s>>>(np, partials, S);
+    if (n > 0) k_pcg_dir<<<grid_for(n), kBlock, 0, s>>>(n, S, z, p);
 }
 
 }  // namespace pamg

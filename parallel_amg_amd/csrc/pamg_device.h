@@ -475,5 +475,22 @@ void launch_fill_xstar(int64_t n, int64_t i0, uint64_t seed, double* y, hipStrea
 // v <- y / diag. partials holds 2 np doubles, np = dot_partials(n).
 void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v, double* partials, int np,
                       double* out, hipStream_t s);
+// The scalars of a device-resident PCG solve (SPEC §S11; pamg_pcg_resident), one block in device
+// memory: rz = (r, z), pq = (p, q), rr = r.r of iteration k; done is set by the first iteration
+// whose rr <= rr_max and never cleared during a solve.
+struct PcgScalars {
+    double rz, pq, alpha, beta, rr, rr_max;
+    int k, done;
+};
+// First half of a §S11 iteration after q = A p: (p, q), alpha = rz / (p, q), x += alpha p,
+// r -= alpha q, rr = r.r, k += 1, rr_hist[k] = rr, done = (rr <= rr_max) — launch_dot's and
+// launch_cg_update's bits with the scalars read from and written to S. Nothing but the
+// partials is touched once S->done is set.
+void launch_pcg_half_a(int64_t n, PcgScalars* S, const double* p, const double* q, double* x, double* r,
+                       double* partials, int np, double* rr_hist, hipStream_t s);
+// Second half after z = M^-1 r: beta = (r, z) / rz, rz = (r, z), p = z + beta p (launch_axpby's
+// bits); the same predicate.
+void launch_pcg_half_b(int64_t n, PcgScalars* S, const double* r, const double* z, double* p, double* partials,
+                       int np, hipStream_t s);
 
 }  // namespace pamg

@@ -10,9 +10,11 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -594,6 +596,18 @@ struct pamg_hier {
     bool graph_failed = false;
     // PCG workspace (level-0 layout, allocated on first use)
     double *pcg_r = nullptr, *pcg_z = nullptr, *pcg_p = nullptr, *pcg_q = nullptr;
+    // device-resident PCG (SPEC §S11, pamg_pcg_resident): the scalar block, the r.r history
+    // (pcg_hist_cap entries), the pinned {k, done} slot the first half of an iteration copies
+    // out, the pinned values the host uploads per solve, the event ring (lookahead + 1), and the
+    // two half-iteration graphs, keyed on the device x (gr_x) like g_x
+    pamg::PcgScalars* pcg_S = nullptr;
+    double* pcg_hist = nullptr;
+    int64_t pcg_hist_cap = 0;
+    int* pcg_slot = nullptr;
+    double* pcg_stage = nullptr;
+    std::vector<hipEvent_t> pcg_ev;
+    hipGraphExec_t g_pcg[2] = {nullptr, nullptr};
+    const double* gr_x = nullptr;
     // level-0 locality permutation (pamg_hier_set_perm): device row i = caller row perm[i];
     // the caller's x and b are gathered into px / pb at entry and x is scattered back at exit
     int* d_perm = nullptr;
@@ -1587,9 +1601,19 @@ static void drop_pipe_graphs(pamg_hier* H) {
     H->gp_x = H->gp_b = nullptr;
 }
 
+// the two half-iteration graphs of pamg_pcg_resident (they hold a whole V-cycle)
+static void drop_pcg_graphs(pamg_hier* H) {
+    for (hipGraphExec_t& g : H->g_pcg) {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
+    }
+    H->gr_x = nullptr;
+}
+
 static void drop_graph(pamg_hier* H) {
     drop_cycle_graph(H);
     drop_pipe_graphs(H);
+    drop_pcg_graphs(H);
 }
 
 int pamg_hier_destroy(pamg_hier* H) {
@@ -1612,6 +1636,11 @@ int pamg_hier_destroy(pamg_hier* H) {
     dfree(H->pcg_z);
     dfree(H->pcg_p);
     dfree(H->pcg_q);
+    dfree(H->pcg_S);
+    dfree(H->pcg_hist);
+    if (H->pcg_slot) (void)hipHostFree(H->pcg_slot);
+    if (H->pcg_stage) (void)hipHostFree(H->pcg_stage);
+    for (auto e : H->pcg_ev) (void)hipEventDestroy(e);
     dfree(H->u0);
     dfree(H->d_perm);
     dfree(H->px);
@@ -2119,6 +2148,216 @@ int pamg_pcg(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* b, double
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(s));
     if (iters) *iters = k;
+    return PAMG_OK;
+}
+
+// SPEC §S11: the largest double c with RN(sqrt(c)) <= thr, so that rr <= c is the test
+// RN(sqrt(rr)) <= thr (RN o sqrt is monotone). Host arithmetic only.
+int pamg_pcg_rr_threshold(double thr, double* out) {
+    if (!out || !(thr >= 0.0)) return fail(PAMG_E_ARG, "pcg_rr_threshold: need thr >= 0 and an output");
+    const double inf = std::numeric_limits<double>::infinity();
+    if (thr == 0.0 || thr == inf) {
+        *out = thr;
+        return PAMG_OK;
+    }
+    double c = thr * thr;  // within a rounding of the answer, save where it underflows or overflows
+    int steps = 0;
+    for (double up = std::nextafter(c, inf); std::sqrt(up) <= thr; up = std::nextafter(c, inf)) {
+        c = up;
+        if (++steps > 4) return fail(PAMG_E_STATE, "pcg_rr_threshold: more than 4 steps up from thr^2 (thr = %a)", thr);
+    }
+    while (std::sqrt(c) > thr) {
+        c = std::nextafter(c, -inf);
+        if (++steps > 4) return fail(PAMG_E_STATE, "pcg_rr_threshold: more than 4 steps down from thr^2 (thr = %a)", thr);
+    }
+    *out = c;
+    return PAMG_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One half of a §S11 iteration on the compute stream. Half 0: q = A p, (p, q), alpha, the x / r
+// update, r.r, the check, and {k, done} to the pinned slot. Half 1: z = M^-1 r, (r, z), beta,
+// p = z + beta p.
+int pcg_half_enqueue(pamg_hier* H, double* xd, int half) {
+    pamg_ctx* ctx = H->ctx;
+    hipStream_t s = ctx->s_comp;
+    const int64_t n = H->A[0]->nrows;
+    const int np = pamg::dot_partials(n);
+    double *r = H->pcg_r, *z = H->pcg_z, *p = H->pcg_p, *q = H->pcg_q;
+    if (half == 0) {
+        CHECK(apply(ctx, H->A[0], pamg::OP_SPMV, p, nullptr, q, 0.0));
+        pamg::launch_pcg_half_a(n, H->pcg_S, p, q, xd, r, ctx->d_red, np, H->pcg_hist, s);
+        HIPC(hipMemcpyAsync(H->pcg_slot, &H->pcg_S->k, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    } else {
+        CHECK(vcycle_enqueue(H, z, r, true));
+        pamg::launch_pcg_half_b(n, H->pcg_S, r, z, p, ctx->d_red, np, s);
+    }
+    HIPC(hipGetLastError());
+    return PAMG_OK;
+}
+
+// Capture the two halves for this device x (once per (H, x), like vcycle_raw's cycle graph); on
+// failure the hierarchy goes to eager launches of the same kernels.
+void pcg_capture(pamg_hier* H, double* xd) {
+    pamg_ctx* ctx = H->ctx;
+    drop_pcg_graphs(H);
+    bool ok = true;
+    for (int half = 0; half < 2 && ok; ++half) {
+        hipGraph_t g = nullptr;
+        if (hipStreamBeginCapture(ctx->s_comp, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+            ok = false;
+            break;
+        }
+        const int rc = pcg_half_enqueue(H, xd, half);
+        const hipError_t e2 = hipStreamEndCapture(ctx->s_comp, &g);
+        ok = rc == PAMG_OK && e2 == hipSuccess && g &&
+             hipGraphInstantiate(&H->g_pcg[half], g, nullptr, nullptr, 0) == hipSuccess;
+        if (g) (void)hipGraphDestroy(g);
+    }
+    if (ok) {
+        H->gr_x = xd;
+        return;
+    }
+    (void)hipGetLastError();
+    drop_pcg_graphs(H);
+    H->use_graph = false;
+    H->graph_failed = true;
+    fprintf(stderr, "[pamg] PCG iteration graph capture failed (%s); using eager launches\n",
+            pamg::last_error().c_str());
+}
+
+}  // namespace
+
+extern "C" {
+
+// Preconditioned CG as pamg_pcg, with alpha, beta, rho and r.r in device memory and the iteration
+// replayed as two graphs (SPEC §S11): the host waits for rr_0, then once per iteration
+// (lookahead 0) or only for the outcome of iteration j - lookahead (lookahead >= 1).
+int pamg_pcg_resident(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* b, double rtol, int maxit,
+                      int lookahead, int* iters, double* res_hist, int stats[2]) {
+    if (!ctx || !H || !x || !b || maxit < 0 || !(rtol >= 0.0) || lookahead < 0 || H->ctx != ctx)
+        return fail(PAMG_E_ARG, "pcg_resident: bad args");
+    if (ctx->nranks > 1)
+        return fail(PAMG_E_STATE, "pcg_resident: one part only (the scalars are not summed across ranks; use pamg_pcg)");
+    const pamg_mat* A = H->A[0];
+    CHECK(check_vec_for(A, x, "pcg_resident"));
+    if (b->n_own != A->nrows) return fail(PAMG_E_ARG, "pcg_resident: b size mismatch");
+    CHECK(set_device(ctx));
+    const int64_t n = A->nrows;
+    int64_t g = A->plan ? A->plan->n_ghost : 0;
+    if (H->L > 1 && H->R[0]->plan) g = std::max(g, H->R[0]->plan->n_ghost);
+    const int64_t cap = n + g + kVecPad;
+    if (!H->pcg_r) {
+        CHECK(dalloc(&H->pcg_r, cap));
+        CHECK(dalloc(&H->pcg_z, cap));
+        CHECK(dalloc(&H->pcg_p, cap));
+        CHECK(dalloc(&H->pcg_q, cap));
+        for (double* p : {H->pcg_r, H->pcg_z, H->pcg_p, H->pcg_q})
+            CHECK(dzero(ctx, p, sizeof(double) * cap));
+    }
+    hipStream_t s = ctx->s_comp;
+    if (!H->pcg_S) {
+        CHECK(dalloc(&H->pcg_S, 1));
+        CHECK(dzero(ctx, H->pcg_S, sizeof(pamg::PcgScalars)));
+        HIPC(hipHostMalloc(reinterpret_cast<void**>(&H->pcg_slot), 2 * sizeof(int)));
+        HIPC(hipHostMalloc(reinterpret_cast<void**>(&H->pcg_stage), 4 * sizeof(double)));
+    }
+    if (H->pcg_hist_cap < (int64_t)maxit + 1) {
+        HIPC(hipStreamSynchronize(s));
+        drop_pcg_graphs(H);  // they carry the history's address
+        dfree(H->pcg_hist);
+        H->pcg_hist_cap = 0;
+        CHECK(dalloc(&H->pcg_hist, (int64_t)maxit + 1));
+        CHECK(dzero(ctx, H->pcg_hist, sizeof(double) * ((size_t)maxit + 1)));
+        H->pcg_hist_cap = (int64_t)maxit + 1;
+    }
+    while ((int)H->pcg_ev.size() < lookahead + 1) {
+        hipEvent_t e = nullptr;
+        HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        H->pcg_ev.push_back(e);
+    }
+    double *r = H->pcg_r, *z = H->pcg_z, *p = H->pcg_p;
+    DeviceSpace d(H, x, b, true);
+    double* xd = d.x;
+    CHECK(apply(ctx, A, pamg::OP_RESID, xd, d.b, r, 0.0));
+    double rr0 = 0.0;
+    CHECK(reduce_scalar(ctx, n, r, r, &rr0));  // the one wait of the prologue
+    const double nr0 = std::sqrt(rr0);
+    int k = 0, enq = 0;
+    if (nr0 > 0.0 && maxit > 0) {
+        // the §S8 test RN(sqrt(rr_k)) <= RN(rtol nr0) as a comparison of rr_k itself
+        double rr_max = 0.0;
+        CHECK(pamg_pcg_rr_threshold(rtol * nr0, &rr_max));
+        static_assert(offsetof(pamg::PcgScalars, k) == offsetof(pamg::PcgScalars, rr_max) + sizeof(double) &&
+                          offsetof(pamg::PcgScalars, done) == offsetof(pamg::PcgScalars, k) + sizeof(int),
+                      "rr_max, k, done are uploaded as one 16-byte piece");
+        H->pcg_stage[0] = rr_max;
+        const int kd[2] = {0, 0};
+        std::memcpy(&H->pcg_stage[1], kd, sizeof(kd));
+        H->pcg_stage[2] = rr0;
+        H->pcg_slot[0] = H->pcg_slot[1] = 0;
+        HIPC(hipMemcpyAsync(&H->pcg_S->rr_max, H->pcg_stage, 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(H->pcg_hist, &H->pcg_stage[2], sizeof(double), hipMemcpyHostToDevice, s));
+        // the first V-cycle goes through vcycle_raw, which allocates whatever the cycle needs (the
+        // Chebyshev rings' spare vector) outside any capture; the captured second halves run the
+        // same zero-guess cycle on the same vectors
+        CHECK(vcycle_raw(H, z, r, 1, true));
+        HIPC(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        const int np = pamg::dot_partials(n);
+        if (np + 1 > ctx->red_cap) return fail(PAMG_E_STATE, "reduction workspace too small");
+        pamg::launch_dot(n, r, z, ctx->d_red, np, &H->pcg_S->rz, s);
+        HIPC(hipGetLastError());
+        if (H->use_graph && !H->prof && (!H->g_pcg[0] || H->gr_x != xd)) pcg_capture(H, xd);
+        const bool replay = H->use_graph && !H->prof && H->g_pcg[0] && H->g_pcg[1];
+        auto half = [&](int h) -> int {
+            if (replay) HIPC(hipGraphLaunch(H->g_pcg[h], s));
+            else CHECK(pcg_half_enqueue(H, xd, h));
+            return PAMG_OK;
+        };
+        const int ring = lookahead + 1;
+        volatile const int* slot = H->pcg_slot;
+        for (int j = 1; j <= maxit; ++j) {
+            CHECK(half(0));
+            ++enq;
+            HIPC(hipEventRecord(H->pcg_ev[j % ring], s));
+            if (lookahead == 0) {
+                // the outcome of this iteration decides whether its second half is enqueued at all
+                HIPC(hipEventSynchronize(H->pcg_ev[j % ring]));
+                if (slot[1]) break;
+                CHECK(half(1));
+                continue;
+            }
+            CHECK(half(1));
+            if (j > lookahead) {
+                // the slot holds iteration j - lookahead's outcome or a later one (done never
+                // clears): at most `lookahead` iterations were enqueued past convergence
+                HIPC(hipEventSynchronize(H->pcg_ev[(j - lookahead) % ring]));
+                if (slot[1]) break;
+            }
+        }
+    }
+    d.finish(x);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+    if (enq > 0) {
+        HIPC(hipMemcpy(&k, &H->pcg_S->k, sizeof(int), hipMemcpyDeviceToHost));
+        if (k < 0 || k > enq) return fail(PAMG_E_STATE, "pcg_resident: iteration counter %d of %d enqueued", k, enq);
+    }
+    if (res_hist) {
+        res_hist[0] = nr0;
+        if (k > 0) {
+            HIPC(hipMemcpy(res_hist + 1, H->pcg_hist + 1, sizeof(double) * k, hipMemcpyDeviceToHost));
+            for (int i = 1; i <= k; ++i) res_hist[i] = std::sqrt(res_hist[i]);
+        }
+    }
+    if (iters) *iters = k;
+    if (stats) {
+        stats[0] = enq;
+        stats[1] = enq - k;
+    }
     return PAMG_OK;
 }
 

@@ -117,6 +117,7 @@ class AMGSolver:
              ptr(self._ainv), int(rep), ptr(roffs) if roffs is not None else None, C.byref(h))
         self._h = h
         self.smoother = "jacobi"
+        self.last_pcg_stats = None
         if self.perm[0] is not None:
             p0 = np.ascontiguousarray(self.perm[0], np.int64)
             call("pamg_hier_set_perm", h, len(p0), ptr(p0))
@@ -230,12 +231,34 @@ class AMGSolver:
         call("pamg_vcycle", self.ctx.handle, self._h, x.handle, b.handle, ncycles, None)
         return None
 
-    def pcg(self, x: PVector, b: PVector, rtol: float = 1e-8, maxit: int = 100):
-        """CG preconditioned by one V-cycle (SPEC §S8); returns (iterations, ||r_k|| history)."""
+    def pcg(self, x: PVector, b: PVector, rtol: float = 1e-8, maxit: int = 100, lookahead: int | None = None):
+        """CG preconditioned by one V-cycle (SPEC §S8); returns (iterations, ||r_k|| history).
+
+        ``lookahead=None`` (default) is ``pamg_pcg``: the scalars on the host, three waits per
+        iteration. An integer takes ``pamg_pcg_resident`` (SPEC §S11, one part only): the scalars stay
+        in device memory and the iteration is replayed as two graphs, with the same bits in x, the
+        count and the history. ``0`` waits once per iteration and runs nothing past convergence;
+        ``L >= 1`` waits only for iteration j - L's outcome and runs up to L iterations (a V-cycle
+        each) past convergence. ``self.last_pcg_stats`` then holds (iterations enqueued, of those
+        after convergence); it is None after a ``lookahead=None`` call.
+
+        Which to take ("Device-resident PCG"; one MI355X, rtol 1e-8): where an iteration
+        is shorter than about a millisecond (poisson3d 128^3, elastic3d 80^3) ``lookahead=0`` is
+        3-4 % faster than ``None``; at 512^3 (8 ms per iteration) the two are level. ``L >= 1`` was
+        never faster than ``0`` — the stream is already fed — and pays its L late iterations: 7-23 %
+        on solves of 9-19 iterations, 1-3 % on 39-66. Use ``0`` for short iterations, ``None`` or
+        ``0`` for long ones, and ``L >= 1`` only where the host thread answers waits slowly."""
         hist = np.zeros(maxit + 1)
         it = C.c_int()
-        call("pamg_pcg", self.ctx.handle, self._h, x.handle, b.handle, float(rtol), int(maxit),
-             C.byref(it), ptr(hist))
+        if lookahead is None:
+            self.last_pcg_stats = None
+            call("pamg_pcg", self.ctx.handle, self._h, x.handle, b.handle, float(rtol), int(maxit),
+                 C.byref(it), ptr(hist))
+        else:
+            stats = (C.c_int * 2)()
+            call("pamg_pcg_resident", self.ctx.handle, self._h, x.handle, b.handle, float(rtol), int(maxit),
+                 int(lookahead), C.byref(it), ptr(hist), stats)
+            self.last_pcg_stats = (int(stats[0]), int(stats[1]))
         return it.value, hist[: it.value + 1]
 
     def vcycle_async(self, x: PVector, b: PVector, ncycles: int = 1):

@@ -14,6 +14,12 @@ A trailing e (j11e, c22e) runs the variant over the estimated bounds of SPEC §S
 
     python tools/cycle_ab.py --pcg j11,j22,j33,c22,c33 --rounds 3 > pcg.jsonl
     python tools/cycle_ab.py --pcg j11,j11e,c22,c22e --rounds 3 > pcg_estimate.jsonl
+
+--lookahead (with --pcg) compares PCG entry points on each variant: none is pamg_pcg, an integer L
+pamg_pcg_resident with that lookahead (SPEC §S11); one JSON line per solve, with the iterations
+enqueued / run past convergence and whether x, the count and the history carry the first solve's bits.
+
+    python tools/cycle_ab.py --pcg j11,c22 --lookahead none,0,1,2 --kind poisson3d --n 128 > pcg_resident.jsonl
 """
 from __future__ import annotations
 
@@ -71,9 +77,22 @@ def main():
     ap.add_argument("--maxit", type=int, default=100)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--lookahead", default=None,
+                    help="with --pcg: entry points to compare, e.g. none,0,1,2 (none = pamg_pcg, an integer = "
+                         "pamg_pcg_resident with that lookahead)")
     a = ap.parse_args()
     if (a.ab is None) == (a.pcg is None):
         ap.error("one of --ab and --pcg")
+    looks = None
+    if a.lookahead is not None:
+        if not a.pcg:
+            ap.error("--lookahead goes with --pcg")
+        try:
+            looks = [None if v == "none" else int(v) for v in a.lookahead.split(",")]
+        except ValueError:
+            ap.error(f"bad --lookahead list {a.lookahead!r}")
+        if any(v is not None and v < 0 for v in looks):
+            ap.error("--lookahead values are none or integers >= 0")
     t0 = time.time()
     ctx = Context(0)
     be = pa.SequentialBackend(1)
@@ -95,15 +114,37 @@ def main():
             S.set_smoother({"j": "jacobi", "c": "chebyshev"}[var[0]], ratio=a.ratio,
                            lmax=est if var.endswith("e") else "gershgorin")
             S.set_sweeps(int(var[1]), int(var[2]))
-            for r in range(-1, a.rounds):  # (-1: warm-up and graph capture)
-                x = S.new_vector()
-                ctx.sync()
-                ts = time.perf_counter()
-                its, hist = S.pcg(x, b, a.rtol, a.maxit)
-                dt = time.perf_counter() - ts
-                if r >= 0:
-                    print(json.dumps({"kind": a.kind, "n": a.n, "variant": var, "round": r, "iterations": its,
-                                      "ms": round(dt * 1e3, 3), "rel_residual": float(hist[-1] / hist[0])}), flush=True)
+            if a.lookahead is None:
+                for r in range(-1, a.rounds):  # (-1: warm-up and graph capture)
+                    x = S.new_vector()
+                    ctx.sync()
+                    ts = time.perf_counter()
+                    its, hist = S.pcg(x, b, a.rtol, a.maxit)
+                    dt = time.perf_counter() - ts
+                    if r >= 0:
+                        print(json.dumps({"kind": a.kind, "n": a.n, "variant": var, "round": r, "iterations": its,
+                                          "ms": round(dt * 1e3, 3), "rel_residual": float(hist[-1] / hist[0])}), flush=True)
+                continue
+            # --lookahead: the entry points round by round (none, 0, 1, ..., none, 0, 1, ...), every
+            # solve into the same zeroed x, so that the resident graphs (keyed on x) are captured in
+            # the warm-up round only
+            x = S.new_vector()
+            ref = None
+            for r in range(-1, a.rounds):
+                for la in looks:
+                    x.fill(0.0)
+                    ctx.sync()
+                    ts = time.perf_counter()
+                    its, hist = S.pcg(x, b, a.rtol, a.maxit, lookahead=la)
+                    dt = time.perf_counter() - ts
+                    # (x is compared too unless downloading it would dwarf the solve)
+                    bits = (its, hist.tobytes(), x.own_values().tobytes() if Af.nrows <= 1 << 24 else None)
+                    ref = ref or bits
+                    if r >= 0:
+                        print(json.dumps({"kind": a.kind, "n": a.n, "variant": var, "lookahead": "none" if la is None else la,
+                                          "round": r, "iterations": its, "ms": round(dt * 1e3, 3),
+                                          "rel_residual": float(hist[-1] / hist[0]), "stats": S.last_pcg_stats,
+                                          "same_bits_as_first": bits == ref}), flush=True)
         return
     key, vals = a.ab.split("=")
     va, vb = (int(v) for v in vals.split(","))
