@@ -229,6 +229,17 @@ int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
  * the mean pair table, out[13] the groups of 4 slices; out[14], out[15] 0. */
 int pamg_mat_ell_window(const pamg_mat* A, int out[16]);
 
+/* Point blocks (SPEC §S12) of a square operator whose rows are node-major (row bs m + d is unknown d of
+ * node m): `blocks` and `inv` are pamg_setup_block_diag's arrays for the own rows (nrows * bs doubles
+ * each: row i's bs entries of its node block D_m, and of D_m^-1), uploaded beside the diagonal. bs = 1
+ * or a NULL array removes them. PAMG_E_ARG for bs outside 1..4, an operator that is not square, or
+ * nrows % bs != 0; PAMG_E_STATE for a matrix uploaded with a permutation (pamg_mat_upload_perm).
+ * Nothing else about the matrix changes: every existing call keeps its bits. A hierarchy that
+ * references the matrix must be told (pamg_hier_set_smoother) after the block data changes. */
+int pamg_mat_set_block_diag(pamg_ctx* ctx, pamg_mat* A, int bs, const double* blocks, const double* inv);
+/* The block size set above (1: no block data). */
+int pamg_mat_block_size(const pamg_mat* A, int* bs);
+
 /* mul!(y, A, x): exchanges x's ghosts (overlapped with the interior rows), then y = A x. */
 int pamg_spmv(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, pamg_vec* y);
 /* r = b - A x ; if nrm2 != NULL, *nrm2 = ||r|| over all parts. */
@@ -267,6 +278,19 @@ int pamg_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec
 int pamg_estimate_lmax(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* v, pamg_vec* y, int steps,
                        int all_parts, double* lam);
 
+/* Point-block forms of the three calls above (SPEC §S12) on a matrix with block data
+ * (pamg_mat_set_block_diag; PAMG_E_STATE without): D^-1 becomes the block-diagonal D_b^-1, applied by
+ * multiplication with the stored inverses — no division. Each sweep is two passes: the residual of the
+ * matrix's own layout, then one pass over the own rows. Arguments and their checks are those of
+ * pamg_jacobi / pamg_chebyshev / pamg_estimate_lmax (x, b and the work vectors must all differ);
+ * lam[k-1] = sum v_i y_i / sum (D_b v)_i v_i, v <- D_b^-1 y. */
+int pamg_block_jacobi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp,
+                      double omega, int nsweeps);
+int pamg_block_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp1,
+                         pamg_vec* tmp2, double lmax, double ratio, int degree);
+int pamg_estimate_lmax_block(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* v, pamg_vec* y, int steps,
+                             int all_parts, double* lam);
+
 /* ------------------------------------------------------------------ hierarchy / V-cycle */
 /* Levels 0..nlevels-1; P[l], R[l] for l < nlevels-1 (NULL entries otherwise). The coarsest
  * level is solved with Ainv (column-major, n_coarse x n_coarse, SPEC §S5).
@@ -298,9 +322,19 @@ int pamg_hier_set_omega(pamg_hier* H, const double* omega);
  * after the coarse correction (the degrees are pamg_hier_set_sweeps'), level l over
  * [lmax[l] / ratio, lmax[l]], lmax holding nlevels - 1 entries (SPEC §S9; lmax[l] > 0, ratio > 1,
  * else PAMG_E_ARG). A Chebyshev hierarchy takes neither the temporally blocked passes nor the
- * cross-cycle pipeline. Changing the smoother drops the captured graphs. */
+ * cross-cycle pipeline. Changing the smoother drops the captured graphs.
+ * PAMG_SMOOTHER_BLOCK_JACOBI / PAMG_SMOOTHER_BLOCK_CHEBYSHEV (SPEC §S12): the same cycle with the
+ * smoother of level l in point-block form where A[l] carries block data (pamg_mat_set_block_diag) and
+ * in the scalar form of the same kind elsewhere; PAMG_E_STATE if no level's matrix carries any. The
+ * Jacobi weights stay pamg_hier_set_omega's, the intervals come from lmax (block Jacobi ignores lmax
+ * and ratio). Like a Chebyshev hierarchy, a block hierarchy takes neither the temporally blocked
+ * passes nor the cross-cycle pipeline. The captured graphs hold the block arrays' addresses: after
+ * changing a referenced matrix's block data call pamg_hier_set_smoother again — with a block kind it
+ * always drops the graphs. */
 #define PAMG_SMOOTHER_JACOBI 0
 #define PAMG_SMOOTHER_CHEBYSHEV 1
+#define PAMG_SMOOTHER_BLOCK_JACOBI 2
+#define PAMG_SMOOTHER_BLOCK_CHEBYSHEV 3
 int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ratio);
 /* Level-0 numbering of a hierarchy whose operators were uploaded with pamg_mat_upload_perm
  * (one part only): device row i of level 0 is caller row perm[i]. pamg_vcycle(_async) and
@@ -461,6 +495,12 @@ int pamg_dev_transpose(pamg_ctx* ctx, const pamg_hcsr* P, int64_t row0, int64_t 
 int pamg_setup_hstack_rows(int k, const pamg_hcsr* const* pieces, pamg_hcsr** out);
 /* Dense Cholesky inverse of a full (single-piece) matrix, column-major out (SPEC §S5). */
 int pamg_setup_cholinv(const pamg_hcsr* A, double* ainv_colmajor);
+/* Point blocks of the own rows (SPEC §S12; A's rows are global rows row0..): row i's bs stored entries
+ * of its node block into blocks[i * bs ..] (absent: 0.0), of the block's §S5 inverse into inv[i * bs ..],
+ * and *rho_b = ||D_b^-1 A||_inf over the own rows. PAMG_E_ARG for bs outside 2..4 or nrows / row0 not
+ * multiples of bs; PAMG_E_SETUP for a block that is not positive definite (the message names it). */
+int pamg_setup_block_diag(const pamg_hcsr* A, int64_t row0, int bs, double* blocks, double* inv,
+                          double* rho_b);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,8 @@ using SparseArrays
 # that does `using PartitionedArrays, PamgHIP` calls them unqualified and unambiguously.
 export Context, ExchangePlan, DeviceVector, DeviceMatrix, HostCSR, VCycle, ExchangeTask, PamgError,
        download_own, download_ghosts, exchange_begin, residual!, jacobi!, jacobi_residual!, chebyshev!, chebyshev_coeffs, vcycle!, pcg!, set_sweeps!, set_smoother!,
-       fill_xstar!, estimate_lmax, set_omega!,
+       fill_xstar!, estimate_lmax, set_omega!, block_diag, set_block_diag!, block_size, block_jacobi!, block_chebyshev!,
+       estimate_lmax_block,
        set_perm!, setup_hierarchy, gen_grid, gen_xstar, read_mtx, rcm_order, locality_order, unique_id,
        comm_init!, runtime_versions, hip, World, world_spmv!, world_exchange!, world_dot, world_vcycle!,
        world_pcg!, world_abort!, world_reset!, world_broken, set_tag!
@@ -469,6 +470,44 @@ function estimate_lmax(A::DeviceMatrix, v::DeviceVector, y::DeviceVector; steps:
                 A.ctx.h, A.h, v.h, y.h, steps, all_parts ? 1 : 0, lam))
     lam
 end
+"""
+    set_block_diag!(A, bs, blocks, inv) / set_block_diag!(A)
+
+Attach the point blocks of the own rows and their inverses (`block_diag`'s bs × nrows matrices, SPEC §S12)
+for the block smoothers, or remove them. A `VCycle` over `A` must be told: `set_smoother!` again.
+"""
+function set_block_diag!(A::DeviceMatrix, bs::Integer, blocks::Matrix{Float64}, inv::Matrix{Float64})
+    check(ccall((:pamg_mat_set_block_diag, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}),
+                A.ctx.h, A.h, bs, blocks, inv))
+    A
+end
+set_block_diag!(A::DeviceMatrix) =
+    (check(ccall((:pamg_mat_set_block_diag, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}),
+                 A.ctx.h, A.h, 1, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL))); A)
+function block_size(A::DeviceMatrix)
+    bs = Ref{Cint}(0)
+    check(ccall((:pamg_mat_block_size, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cint}), A.h, bs))
+    Int(bs[])
+end
+"nsweeps point-block Jacobi sweeps x <- x + ω D_b⁻¹ (b - A x) (SPEC §S12; `A` carries block data)."
+block_jacobi!(x::DeviceVector, A::DeviceMatrix, b::DeviceVector, tmp::DeviceVector, omega::Real, nsweeps::Integer = 1) =
+    (check(ccall((:pamg_block_jacobi, libpamg), Cint,
+                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint),
+                 A.ctx.h, A.h, x.h, b.h, tmp.h, omega, nsweeps)); x)
+"`chebyshev!` with the inverse node blocks D_b⁻¹ for D⁻¹ (SPEC §S12)."
+block_chebyshev!(x::DeviceVector, A::DeviceMatrix, b::DeviceVector, tmp1::DeviceVector, tmp2::DeviceVector, lmax::Real;
+                 ratio::Real = 4.0, degree::Integer = 2) =
+    (check(ccall((:pamg_block_chebyshev, libpamg), Cint,
+                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint),
+                 A.ctx.h, A.h, x.h, b.h, tmp1.h, tmp2.h, lmax, ratio, degree)); x)
+"`estimate_lmax` for λmax(D_b⁻¹A) (SPEC §S12)."
+function estimate_lmax_block(A::DeviceMatrix, v::DeviceVector, y::DeviceVector; steps::Integer = 10, all_parts::Bool = true)
+    lam = zeros(Float64, max(steps, 1))
+    check(ccall((:pamg_estimate_lmax_block, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Float64}),
+                A.ctx.h, A.h, v.h, y.h, steps, all_parts ? 1 : 0, lam))
+    lam
+end
 "t = x + ω D⁻¹ (b - A x), r = b - A t (one fused pass where the matrix qualifies); returns whether it fused."
 function jacobi_residual!(t::DeviceVector, r::DeviceVector, A::DeviceMatrix, x::DeviceVector, b::DeviceVector, omega::Real)
     f = Ref{Cint}(0)
@@ -658,13 +697,17 @@ set_sweeps!(M::VCycle, nu1::Integer, nu2::Integer) =
 The V-cycle's smoother: `:jacobi` (default) or `:chebyshev` — one polynomial of degree nu1 before
 and nu2 after the coarse correction (`set_sweeps!` gives the degrees), level l over
 [lmax[l] / ratio, lmax[l]] (SPEC §S9). `lmax` needs an entry for every level but the coarsest.
+`:block_jacobi` / `:block_chebyshev` (SPEC §S12): the same with the inverse node blocks for D⁻¹ on the
+levels whose matrix carries block data (`set_block_diag!`); pass the block levels' own bounds
+(`block_diag`'s rho_b or `estimate_lmax_block`) in `lmax`, and their weights through `set_omega!`.
 """
 function set_smoother!(M::VCycle, kind::Symbol; ratio::Real = 4.0, lmax::Vector{Float64} = M.rho)
-    k = Dict(:jacobi => 0, :chebyshev => 1)[kind]
+    k = Dict(:jacobi => 0, :chebyshev => 1, :block_jacobi => 2, :block_chebyshev => 3)[kind]
     nl = length(M.A) - 1
-    k == 0 || length(lmax) >= nl || throw(DimensionMismatch("set_smoother!: lmax needs $nl entries"))
+    jac = k == 0 || k == 2
+    jac || length(lmax) >= nl || throw(DimensionMismatch("set_smoother!: lmax needs $nl entries"))
     check(ccall((:pamg_hier_set_smoother, libpamg), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Cdouble), M.h, k,
-                k == 0 || nl == 0 ? Ptr{Float64}(C_NULL) : lmax, ratio))
+                jac || nl == 0 ? Ptr{Float64}(C_NULL) : lmax, ratio))
     M
 end
 "Replace the Jacobi weights of every level but the coarsest (e.g. 4 / (3 lmax_l) with an estimated bound, SPEC §S10)."
@@ -864,6 +907,20 @@ function hstack_rows(pieces::Vector{HostCSR})
     ps = Ptr{Cvoid}[p.h for p in pieces]
     check(ccall((:pamg_setup_hstack_rows, libpamg), Cint, (Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}), length(ps), ps, h))
     HostCSR(h[])
+end
+"""
+    block_diag(A, row0, bs) -> (blocks, inv, rho_b)
+
+The point blocks of A's rows (global rows row0.., 0-based; SPEC §S12) as bs × nrows matrices — column i
+holds row i's bs entries of its node block D_m, and of the block's §S5 inverse — and ‖D_b⁻¹A‖_∞.
+"""
+function block_diag(A::HostCSR, row0::Integer, bs::Integer)
+    n = size(A, 1)
+    blocks, inv = zeros(Float64, max(bs, 1), n), zeros(Float64, max(bs, 1), n)
+    rho = Ref{Cdouble}(0.0)
+    check(ccall((:pamg_setup_block_diag, libpamg), Cint, (Ptr{Cvoid}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Cdouble}),
+                A.h, row0, bs, blocks, inv, rho))
+    (blocks, inv, rho[])
 end
 function cholinv(A::HostCSR)
     n = size(A, 1)

@@ -84,6 +84,8 @@ SIGNATURES = {
     "pamg_mat_stream_bytes": [vp, pi64],
     "pamg_mat_layout": [vp, i32, C.POINTER(C.c_int)],
     "pamg_mat_ell_window": [vp, C.POINTER(C.c_int)],
+    "pamg_mat_set_block_diag": [vp, vp, i32, vp, vp],
+    "pamg_mat_block_size": [vp, C.POINTER(C.c_int)],
     "pamg_spmv": [vp, vp, vp, vp],
     "pamg_residual": [vp, vp, vp, vp, vp, pdbl],
     "pamg_jacobi": [vp, vp, vp, vp, vp, dbl, i32],
@@ -91,6 +93,9 @@ SIGNATURES = {
     "pamg_chebyshev_coeffs": [dbl, dbl, i32, vp, vp],
     "pamg_chebyshev": [vp, vp, vp, vp, vp, vp, dbl, dbl, i32],
     "pamg_estimate_lmax": [vp, vp, vp, vp, i32, i32, vp],
+    "pamg_block_jacobi": [vp, vp, vp, vp, vp, dbl, i32],
+    "pamg_block_chebyshev": [vp, vp, vp, vp, vp, vp, dbl, dbl, i32],
+    "pamg_estimate_lmax_block": [vp, vp, vp, vp, i32, i32, vp],
     "pamg_hier_set_omega": [vp, vp],
     "pamg_hier_create": [vp, i32, vp, vp, vp, vp, i64, vp, i32, vp, pvp],
     "pamg_hier_destroy": [vp],
@@ -131,6 +136,7 @@ SIGNATURES = {
     "pamg_dev_transpose": [vp, vp, i64, i64, i64, pvp],
     "pamg_setup_hstack_rows": [i32, vp, pvp],
     "pamg_setup_cholinv": [vp, vp],
+    "pamg_setup_block_diag": [vp, i64, i32, vp, vp, pdbl],
 }
 _RESTYPE = {"pamg_version": C.c_char_p, "pamg_last_error": C.c_char_p}
 

@@ -2666,6 +2666,105 @@ __global__ __launch_bounds__(kBlock) void k_lmax_step(int64_t n, const double* _
     }
 }
 
+// Point-block smoothing (SPEC §S12): the second pass of a block sweep. The first pass wrote the residual
+// u = b - A x (OP_RESID of whatever layout the matrix has) into y; this one turns it into the new iterate
+// in place. A workgroup owns a run of kBlkRun consecutive rows — whole blocks, 768 = 256 lanes x 3 rows
+// divides by 2, 3 and 4 — stages the run's u in LDS with coalesced loads, and after the barrier every lane
+// forms w_i = sum_j Dinv_ij u_j (products and adds rounded one by one, j ascending from +0.0) for its
+// rows from LDS and its own Dinv row, then stores coalesced. A run's u is read by its own workgroup only
+// and wholly before the barrier, so u may be y. No division anywhere. Modes (BlockMode, pamg_device.h):
+//   BM_JACOBI  y_i = x_i + c2 w_i                        (block Jacobi; Chebyshev step 0)
+//   BM_ZERO    u_i = u_i - 0.0 on load (u is b); y_i = 0.0 + c2 w_i        (zero guess)
+//   BM_CHEB    y_i = x_i + (c1 (x_i - xold_i) + c2 w_i)  (Chebyshev step k >= 1; null xold: zeros)
+//   BM_SOLVE   y_i = w_i                                 (the block estimate's v <- D_b^-1 y)
+constexpr int kBlkRows = 3;
+constexpr int kBlkRun = kBlock * kBlkRows;
+template <int BS, int MODE>
+__global__ __launch_bounds__(kBlock) void k_block_update(int64_t n, const double* u, const double* __restrict__ binv,
+                                                         const double* __restrict__ x,
+                                                         const double* __restrict__ xold, double* y, double c1,
+                                                         double c2) {
+    static_assert(kBlkRun % BS == 0, "a run holds whole blocks");
+    __shared__ double lu[kBlkRun];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * kBlkRun;
+    const int64_t left = n - base;  // (n is a multiple of BS, so is base: the last run ends on a block)
+    const int nr = left < kBlkRun ? (int)left : kBlkRun;
+#pragma unroll
+    for (int k = 0; k < kBlkRows; ++k) {
+        const int l = tid + k * kBlock;
+        if (l < nr) {
+            double ui = u[base + l];
+            if constexpr (MODE == BM_ZERO) ui = ui - 0.0;
+            lu[l] = ui;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kBlkRows; ++k) {
+        const int l = tid + k * kBlock;
+        if (l >= nr) continue;
+        const int64_t r = base + l;
+        const int m0 = l - l % BS;
+        const double* di = binv + r * BS;
+        double w = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) {
+            const double p = di[j] * lu[m0 + j];
+            w = w + p;
+        }
+        if constexpr (MODE == BM_SOLVE) {
+            y[r] = w;
+        } else if constexpr (MODE == BM_ZERO) {
+            const double v = c2 * w;
+            y[r] = 0.0 + v;
+        } else if constexpr (MODE == BM_JACOBI) {
+            const double v = c2 * w;
+            y[r] = x[r] + v;
+        } else {
+            const double xi = x[r];
+            const double v = c2 * w;
+            const double e = xi - (xold ? xold[r] : 0.0);
+            const double q = c1 * e;
+            const double t = q + v;
+            y[r] = xi + t;
+        }
+    }
+}
+
+// The sums of a SPEC §S12 estimate step after y = A v: the partials of v.y and of (D_b v).v, in
+// k_lmax_step's grid-stride order and block_sum tree. Row i's (D_b v)_i reads the v of its whole block,
+// rows other lanes and workgroups own, so nothing is written here: v <- D_b^-1 y is the pass after
+// (k_block_update<BS, BM_SOLVE>).
+template <int BS>
+__global__ __launch_bounds__(kBlock) void k_lmax_step_block(int64_t n, const double* __restrict__ y,
+                                                            const double* __restrict__ bdiag,
+                                                            const double* __restrict__ v, double* __restrict__ pnum,
+                                                            double* __restrict__ pden) {
+    __shared__ double lds[2][kBlock / 64];
+    double a = 0.0, c = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * kBlock) {
+        const int64_t m0 = i - i % BS;
+        const double* di = bdiag + i * BS;
+        double dv = 0.0;
+#pragma unroll
+        for (int j = 0; j < BS; ++j) {
+            const double p = di[j] * v[m0 + j];
+            dv = dv + p;
+        }
+        const double vi = v[i];
+        a += vi * y[i];
+        c += dv * vi;
+    }
+    const double sa = block_sum(a, lds[0]);
+    const double sc = block_sum(c, lds[1]);
+    if (threadIdx.x == 0) {
+        pnum[blockIdx.x] = sa;
+        pden[blockIdx.x] = sc;
+    }
+}
+
 inline int grid_for(int64_t n, int cap = 8192) {
     int64_t g = (n + kBlock - 1) / kBlock;
     if (g < 1) g = 1;
@@ -3174,6 +3273,41 @@ void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v,
     k_lmax_step<<<np, kBlock, 0, s>>>(n, y, diag, v, partials, partials + np);
     k_dot_final<<<1, kBlock, 0, s>>>(np, partials, out);
     k_dot_final<<<1, kBlock, 0, s>>>(np, partials + np, out + 1);
+}
+
+template <int BS>
+static void launch_block_update_bs(int64_t n, int mode, const double* u, const double* binv, const double* x,
+                                   const double* xold, double* y, double c1, double c2, hipStream_t s) {
+    const int grid = (int)((n + kBlkRun - 1) / kBlkRun);
+    switch (mode) {
+        case BM_JACOBI: k_block_update<BS, BM_JACOBI><<<grid, kBlock, 0, s>>>(n, u, binv, x, xold, y, c1, c2); break;
+        case BM_ZERO: k_block_update<BS, BM_ZERO><<<grid, kBlock, 0, s>>>(n, u, binv, x, xold, y, c1, c2); break;
+        case BM_CHEB: k_block_update<BS, BM_CHEB><<<grid, kBlock, 0, s>>>(n, u, binv, x, xold, y, c1, c2); break;
+        default: k_block_update<BS, BM_SOLVE><<<grid, kBlock, 0, s>>>(n, u, binv, x, xold, y, c1, c2); break;
+    }
+}
+
+void launch_block_update(const pamg_mat& A, int mode, const double* u, const double* x, const double* xold, double* y,
+                         double c1, double c2, hipStream_t s) {
+    if (A.nrows <= 0) return;
+    switch (A.bs) {
+        case 2: launch_block_update_bs<2>(A.nrows, mode, u, A.d_binv, x, xold, y, c1, c2, s); break;
+        case 3: launch_block_update_bs<3>(A.nrows, mode, u, A.d_binv, x, xold, y, c1, c2, s); break;
+        default: launch_block_update_bs<4>(A.nrows, mode, u, A.d_binv, x, xold, y, c1, c2, s); break;
+    }
+}
+
+void launch_lmax_step_block(const pamg_mat& A, const double* y, double* v, double* partials, int np, double* out,
+                            hipStream_t s) {
+    const int64_t n = A.nrows;
+    switch (A.bs) {
+        case 2: k_lmax_step_block<2><<<np, kBlock, 0, s>>>(n, y, A.d_bdiag, v, partials, partials + np); break;
+        case 3: k_lmax_step_block<3><<<np, kBlock, 0, s>>>(n, y, A.d_bdiag, v, partials, partials + np); break;
+        default: k_lmax_step_block<4><<<np, kBlock, 0, s>>>(n, y, A.d_bdiag, v, partials, partials + np); break;
+    }
+    k_dot_final<<<1, kBlock, 0, s>>>(np, partials, out);
+    k_dot_final<<<1, kBlock, 0, s>>>(np, partials + np, out + 1);
+    launch_block_update(A, BM_SOLVE, y, nullptr, nullptr, v, 0.0, 0.0, s);
 }
 
 void launch_pcg_half_a(int64_t n, PcgScalars* S, const double* p, const double* q, double* x, double* r,

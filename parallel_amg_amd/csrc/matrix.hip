@@ -2726,7 +2726,58 @@ int pamg_mat_upload_perm(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int6
         }
     });
     if (bad) return fail(PAMG_E_ARG, "mat_upload_perm: column out of range");
-    return pamg_mat_upload(ctx, nrows, ncols, rp.data(), ci.data(), 0, va.data(), 0, plan, out);
+    CHECK(pamg_mat_upload(ctx, nrows, ncols, rp.data(), ci.data(), 0, va.data(), 0, plan, out));
+    (*out)->permuted = row_perm || col_perm;
+    return PAMG_OK;
+}
+
+// SPEC §S12: the node blocks of the own rows and their inverses (pamg_setup_block_diag's arrays, nrows * bs
+// doubles each), kept beside d_diag. Device rows must be the caller's rows: a permuted upload scatters the
+// nodes' rows, so it is refused.
+int pamg_mat_set_block_diag(pamg_ctx* ctx, pamg_mat* A, int bs, const double* blocks, const double* inv) {
+    if (!ctx || !A || A->ctx != ctx) return fail(PAMG_E_ARG, "mat_set_block_diag: bad context or matrix");
+    (void)hipSetDevice(ctx->device);
+    if (bs == 1 || !blocks || !inv) {
+        if (bs != 1 && (bs < 2 || bs > 4)) return fail(PAMG_E_ARG, "mat_set_block_diag: block size %d outside 1..4", bs);
+        HIPC(hipStreamSynchronize(ctx->s_comp));  // (a sweep still in flight reads the arrays)
+        dfree(A->d_bdiag);
+        dfree(A->d_binv);
+        A->d_bdiag = A->d_binv = nullptr;
+        A->bs = 1;
+        return PAMG_OK;
+    }
+    if (bs < 2 || bs > 4) return fail(PAMG_E_ARG, "mat_set_block_diag: block size %d outside 1..4", bs);
+    const int64_t n_own_cols = A->plan ? A->plan->n_own : A->ncols;
+    if (A->nrows != n_own_cols)
+        return fail(PAMG_E_ARG, "mat_set_block_diag: the operator must be square (%lld rows, %lld own columns)",
+                    (long long)A->nrows, (long long)n_own_cols);
+    if (A->nrows % bs != 0)
+        return fail(PAMG_E_ARG, "mat_set_block_diag: %lld rows are not whole blocks of %d", (long long)A->nrows, bs);
+    if (A->permuted)
+        return fail(PAMG_E_STATE, "mat_set_block_diag: the matrix was uploaded with a permutation (its rows are not "
+                    "in node order)");
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    dfree(A->d_bdiag);
+    dfree(A->d_binv);
+    A->d_bdiag = A->d_binv = nullptr;
+    A->bs = 1;
+    if (A->nrows == 0) {
+        A->bs = bs;
+        return PAMG_OK;
+    }
+    const size_t cnt = (size_t)A->nrows * bs;
+    CHECK(dalloc(&A->d_bdiag, cnt));
+    CHECK(dalloc(&A->d_binv, cnt));
+    CHECK(h2d(ctx, A->d_bdiag, blocks, sizeof(double) * cnt));
+    CHECK(h2d(ctx, A->d_binv, inv, sizeof(double) * cnt));
+    A->bs = bs;
+    return PAMG_OK;
+}
+
+int pamg_mat_block_size(const pamg_mat* A, int* bs) {
+    if (!A || !bs) return fail(PAMG_E_ARG, "mat_block_size: bad args");
+    *bs = A->bs;
+    return PAMG_OK;
 }
 
 int pamg_mat_destroy(pamg_mat* A) {
@@ -2743,6 +2794,8 @@ int pamg_mat_destroy(pamg_mat* A) {
     dfree(A->d_anc16);
     dfree(A->d_val);
     dfree(A->d_diag);
+    dfree(A->d_bdiag);
+    dfree(A->d_binv);
     sym_free(A->sym);
     tiles_free(A->interior);
     tiles_free(A->boundary);

@@ -415,6 +415,12 @@ struct pamg_mat {
     uint16_t* d_anc16 = nullptr;  // per-tile anchored dictionaries: row's first column - tile base
     double* d_val = nullptr;
     double* d_diag = nullptr;  // a_ii for square matrices (zero-guess Jacobi), else null
+    // point blocks (SPEC §S12; pamg_mat_set_block_diag): bs = 1 none; else row i's bs entries of its node
+    // block D_m at d_bdiag[i * bs ..] and of D_m^-1 at d_binv[i * bs ..], beside d_diag
+    bool permuted = false;  // uploaded through pamg_mat_upload_perm with a row or column permutation
+    int bs = 1;
+    double* d_bdiag = nullptr;
+    double* d_binv = nullptr;
     const pamg_plan* plan = nullptr;
     pamg::SymDia sym;        // the interior set's symmetric diagonal-class layout (TileSet::sym)
     pamg::TileSet interior;  // rows with own columns only (overlap with the exchange)
@@ -475,6 +481,17 @@ void launch_fill_xstar(int64_t n, int64_t i0, uint64_t seed, double* y, hipStrea
 // v <- y / diag. partials holds 2 np doubles, np = dot_partials(n).
 void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v, double* partials, int np,
                       double* out, hipStream_t s);
+// SPEC §S12, the second pass of a point-block sweep (k_block_update; A carries block data): u holds the
+// residual b - A x of the own rows (mode BM_ZERO: b itself) and may be y; w = D_b^-1 u per block, then
+// BM_JACOBI y = x + c2 w, BM_ZERO y = 0.0 + c2 w, BM_CHEB y = x + (c1 (x - xold) + c2 w) (null xold:
+// zeros), BM_SOLVE y = w. Own rows only.
+enum BlockMode : int { BM_JACOBI = 0, BM_ZERO = 1, BM_CHEB = 2, BM_SOLVE = 3 };
+void launch_block_update(const pamg_mat& A, int mode, const double* u, const double* x, const double* xold, double* y,
+                         double c1, double c2, hipStream_t s);
+// SPEC §S12 estimate step after y = A v: out[0] = v.y, out[1] = (D_b v).v (launch_lmax_step's order and
+// trees), then v <- D_b^-1 y in a pass of its own. partials holds 2 np doubles.
+void launch_lmax_step_block(const pamg_mat& A, const double* y, double* v, double* partials, int np, double* out,
+                            hipStream_t s);
 // The scalars of a device-resident PCG solve (SPEC §S11; pamg_pcg_resident), one block in device
 // memory: rz = (r, z), pq = (p, q), rr = r.r of iteration k; done is set by the first iteration
 // whose rr <= rr_max and never cleared during a solve.

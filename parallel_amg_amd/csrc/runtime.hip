@@ -356,6 +356,23 @@ int apply(pamg_ctx* ctx, const pamg_mat* A, int op, double* x, const double* b, 
         [&]() { pamg::launch_rows(*A, A->boundary, op, x, b, xold, y, omega, s, c1); });
 }
 
+// One smoothing step in point-block form (SPEC §S12) on an operator that carries block data: the residual
+// b - A x of the layout's own OP_RESID into y (x's ghosts exchanged by apply), then the block pass over
+// the own rows turns y into the new iterate in place. BM_ZERO reads b alone (no row sums); y differs
+// from x and xold.
+int block_step(pamg_ctx* ctx, const pamg_mat* A, int mode, double* x, const double* b, const double* xold, double* y,
+               double c1, double c2) {
+    hipStream_t s = ctx->s_comp;
+    if (mode == pamg::BM_ZERO) {
+        pamg::launch_block_update(*A, mode, b, nullptr, nullptr, y, 0.0, c2, s);
+    } else {
+        CHECK(apply(ctx, A, pamg::OP_RESID, x, b, y, 0.0));
+        pamg::launch_block_update(*A, mode, y, x, xold, y, c1, c2, s);
+    }
+    HIPC(hipGetLastError());
+    return PAMG_OK;
+}
+
 // SPEC §S9 coefficients of a degree-m polynomial over [lmax / ratio, lmax]: fp64, one rounded
 // operation each, in the order the specification fixes (built with -ffp-contract=off)
 constexpr int kChebMaxDeg = 64;
@@ -379,14 +396,17 @@ void cheb_coeffs(double lmax, double ratio, int m, double* c1, double* c2) {
 // of which is `in` or b unless the caller knows `in` dead by then: step k writes ring[k % 3], reads
 // x_k = ring[(k - 1) % 3] and x_{k-1} = ring[(k - 2) % 3] (k = 1: in), so y never aliases x or
 // xold. Returns the vector holding x_m.
+// block: the steps in point-block form (SPEC §S12; A carries block data), else §S9's.
 int cheb_poly(pamg_ctx* ctx, const pamg_mat* A, int64_t nown, const double* c1, const double* c2, int m, double* in,
-              const double* b, double* const ring[3], double** out) {
+              const double* b, double* const ring[3], double** out, bool block = false) {
     hipStream_t s = ctx->s_comp;
-    if (in) CHECK(apply(ctx, A, pamg::OP_JACOBI, in, b, ring[0], c2[0]));
+    if (block) CHECK(block_step(ctx, A, in ? pamg::BM_JACOBI : pamg::BM_ZERO, in, b, nullptr, ring[0], 0.0, c2[0]));
+    else if (in) CHECK(apply(ctx, A, pamg::OP_JACOBI, in, b, ring[0], c2[0]));
     else pamg::launch_jacobi_zero(nown, b, A->d_diag, c2[0], ring[0], s);
     for (int k = 1; k < m; ++k) {
         const double* xo = k == 1 ? in : ring[(k - 2) % 3];
-        CHECK(apply(ctx, A, pamg::OP_CHEB, ring[(k - 1) % 3], b, ring[k % 3], c2[k], c1[k], xo));
+        if (block) CHECK(block_step(ctx, A, pamg::BM_CHEB, ring[(k - 1) % 3], b, xo, ring[k % 3], c1[k], c2[k]));
+        else CHECK(apply(ctx, A, pamg::OP_CHEB, ring[(k - 1) % 3], b, ring[k % 3], c2[k], c1[k], xo));
     }
     *out = ring[(m - 1) % 3];
     return PAMG_OK;
@@ -527,13 +547,15 @@ int reduce_scalar(pamg_ctx* ctx, int64_t n, const double* x, const double* y, do
 // The two sums of a SPEC §S10 step after y = A v, with v <- y / diag in the same pass:
 // out[0] = sum v_i y_i, out[1] = sum (a_ii v_i) v_i over the own rows — of every rank when
 // all_parts (the cross-rank sums of reduce_with), else of this rank alone (a level held whole).
+// blk (SPEC §S12): the block form on that operator's data — (D_b v).v and v <- D_b^-1 y.
 int lmax_sums(pamg_ctx* ctx, int64_t n, const double* y, const double* diag, double* v, bool all_parts,
-              double out[2]) {
+              double out[2], const pamg_mat* blk = nullptr) {
     hipStream_t s = ctx->s_comp;
     const int np = pamg::dot_partials(n);
     if (2 * np + 2 > ctx->red_cap) return fail(PAMG_E_STATE, "reduction workspace too small");
     double* res = ctx->d_red + ctx->red_cap - 2;
-    pamg::launch_lmax_step(n, y, diag, v, ctx->d_red, np, res, s);
+    if (blk) pamg::launch_lmax_step_block(*blk, y, v, ctx->d_red, np, res, s);
+    else pamg::launch_lmax_step(n, y, diag, v, ctx->d_red, np, res, s);
     HIPC(hipGetLastError());
     const bool cross = all_parts && ctx->nranks > 1;
     if (cross && ctx->comm) NCCLC(ncclAllReduce(res, res, 2, ncclDouble, ncclSum, ctx->comm, s));
@@ -710,6 +732,15 @@ struct L0Seg {
     bool post = true;
 };
 
+bool cheb_kind(const pamg_hier* H) {
+    return H->smoother == PAMG_SMOOTHER_CHEBYSHEV || H->smoother == PAMG_SMOOTHER_BLOCK_CHEBYSHEV;
+}
+// SPEC §S12 "in the cycle": level l smooths in block form under a block smoother where A_l carries block data
+bool block_level(const pamg_hier* H, int l) {
+    return (H->smoother == PAMG_SMOOTHER_BLOCK_JACOBI || H->smoother == PAMG_SMOOTHER_BLOCK_CHEBYSHEV) &&
+           H->A[l]->bs > 1;
+}
+
 int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false, L0Seg seg = L0Seg{}) {
     pamg_ctx* ctx = H->ctx;
     hipStream_t s = ctx->s_comp;
@@ -729,7 +760,8 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
     // iterate of a level >= 1 ends in whichever of them the degrees select (xres, read by the
     // prolongation above it); on level 0 it must end in the caller's x, which the choice of the
     // rings arranges (with the spare u0 where the two degrees' remainders mod 3 disagree, need_u0)
-    const bool cheb = H->smoother == PAMG_SMOOTHER_CHEBYSHEV;
+    const bool cheb = cheb_kind(H);
+    const bool blocks = H->smoother == PAMG_SMOOTHER_BLOCK_JACOBI || H->smoother == PAMG_SMOOTHER_BLOCK_CHEBYSHEV;
     std::vector<double*> xres(H->x);
     auto others = [&](int l, const double* not_this, double* out[4]) {  // the level's vectors, x[l] last
         int n = 0;
@@ -750,7 +782,8 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
         // level 0, V(1, nu2) from a given guess: the pre-smoothing sweep and the residual in one
         // temporally blocked pass where the operator has one (jacobi_residual; both timed as
         // jacobi_pre)
-        const bool fuse = !cheb && l == 0 && !zero0 && H->nu1 == 1 && jr_blocked(A) != 0;
+        const bool fuse = !cheb && !blocks && l == 0 && !zero0 && H->nu1 == 1 && jr_blocked(A) != 0;
+        const bool blk = block_level(H, l);
         if (cheb) {
             ProfScope p(H, l, 0, s);
             double* in = l == 0 && !zero0 ? H->x[0] : nullptr;
@@ -768,7 +801,7 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
             }
             if (!ring[2]) return fail(PAMG_E_STATE, "vcycle: the Chebyshev cycle lacks its spare level-0 vector");
             CHECK(cheb_poly(ctx, A, H->nown[l], H->cheb_c1[l].data(), H->cheb_c2[l].data(), H->nu1, in, H->b[l], ring,
-                            &c));
+                            &c, blk));
             double* oth[4];
             others(l, c, oth);
             o = oth[0];
@@ -778,12 +811,16 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
             CHECK(jacobi_residual(ctx, A, H->x[0], H->b[0], c, o, H->omega[0], &fused));
         } else {
             ProfScope p(H, l, 0, s);
-            if (l == 0 && !zero0)
+            if (blk)
+                CHECK(block_step(ctx, A, l == 0 && !zero0 ? pamg::BM_JACOBI : pamg::BM_ZERO, H->x[0], H->b[l], nullptr, c,
+                                 0.0, H->omega[l]));
+            else if (l == 0 && !zero0)
                 CHECK(apply(ctx, A, pamg::OP_JACOBI, H->x[0], H->b[0], c, H->omega[0]));
             else
                 pamg::launch_jacobi_zero(H->nown[l], H->b[l], A->d_diag, H->omega[l], c, s);
             for (int k = 1; k < H->nu1; ++k) {
-                CHECK(apply(ctx, A, pamg::OP_JACOBI, c, H->b[l], o, H->omega[l]));
+                if (blk) CHECK(block_step(ctx, A, pamg::BM_JACOBI, c, H->b[l], nullptr, o, 0.0, H->omega[l]));
+                else CHECK(apply(ctx, A, pamg::OP_JACOBI, c, H->b[l], o, H->omega[l]));
                 std::swap(c, o);
             }
         }
@@ -828,14 +865,17 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
                 ring[1 - last] = oth[0];
             }
             CHECK(cheb_poly(ctx, H->A[l], H->nown[l], H->cheb_c1[l].data(), H->cheb_c2[l].data(), H->nu2, cur[l],
-                            H->b[l], ring, &xres[l]));
+                            H->b[l], ring, &xres[l], block_level(H, l)));
             if (l == 0 && xres[0] != H->x[0]) return fail(PAMG_E_STATE, "vcycle: Chebyshev ring order");
         } else {
             ProfScope p(H, l, 4, s);
             double* in = cur[l];
             for (int k = 0; k < H->nu2; ++k) {
                 double* out = ((H->nu2 - k) % 2 == 1) ? H->x[l] : spare[l];
-                CHECK(apply(ctx, H->A[l], pamg::OP_JACOBI, in, H->b[l], out, H->omega[l]));
+                if (block_level(H, l))
+                    CHECK(block_step(ctx, H->A[l], pamg::BM_JACOBI, in, H->b[l], nullptr, out, 0.0, H->omega[l]));
+                else
+                    CHECK(apply(ctx, H->A[l], pamg::OP_JACOBI, in, H->b[l], out, H->omega[l]));
                 if (out == spare[l]) spare[l] = in;
                 in = out;
             }
@@ -1694,11 +1734,20 @@ int pamg_hier_set_omega(pamg_hier* H, const double* omega) {
 }
 
 int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ratio) {
-    if (!H || (kind != PAMG_SMOOTHER_JACOBI && kind != PAMG_SMOOTHER_CHEBYSHEV))
+    if (!H || kind < PAMG_SMOOTHER_JACOBI || kind > PAMG_SMOOTHER_BLOCK_CHEBYSHEV)
         return fail(PAMG_E_ARG, "hier_set_smoother: bad hierarchy or smoother kind");
     const int nl = H->L - 1;
+    const bool is_block = kind == PAMG_SMOOTHER_BLOCK_JACOBI || kind == PAMG_SMOOTHER_BLOCK_CHEBYSHEV;
+    const bool is_cheb = kind == PAMG_SMOOTHER_CHEBYSHEV || kind == PAMG_SMOOTHER_BLOCK_CHEBYSHEV;
+    if (is_block) {
+        bool any = false;
+        for (int l = 0; l < nl; ++l) any = any || H->A[l]->bs > 1;
+        if (!any)
+            return fail(PAMG_E_STATE, "hier_set_smoother: a block smoother needs block data on a level's matrix "
+                        "(pamg_mat_set_block_diag)");
+    }
     std::vector<double> lm;
-    if (kind == PAMG_SMOOTHER_CHEBYSHEV) {
+    if (is_cheb) {
         if (!(ratio > 1.0) || !std::isfinite(ratio)) return fail(PAMG_E_ARG, "hier_set_smoother: ratio must be > 1");
         if (nl > 0 && !lmax) return fail(PAMG_E_ARG, "hier_set_smoother: lmax is NULL");
         for (int l = 0; l < nl; ++l) {
@@ -1707,7 +1756,9 @@ int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ra
             lm.push_back(lmax[l]);
         }
     }
-    const bool same = kind == H->smoother && (kind == PAMG_SMOOTHER_JACOBI || (lm == H->cheb_lmax && ratio == H->cheb_ratio));
+    // (a block smoother always drops: the matrices' block data may have changed since the capture)
+    const bool same = !is_block && kind == H->smoother &&
+                      (kind == PAMG_SMOOTHER_JACOBI || (lm == H->cheb_lmax && ratio == H->cheb_ratio));
     if (!same) {
         (void)hipSetDevice(H->ctx->device);
         (void)hipStreamSynchronize(H->ctx->s_comp);
@@ -1717,7 +1768,7 @@ int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ra
     H->cheb_lmax.clear();
     H->cheb_c1.clear();
     H->cheb_c2.clear();
-    if (kind == PAMG_SMOOTHER_CHEBYSHEV) {
+    if (is_cheb) {
         H->cheb_ratio = ratio;
         H->cheb_lmax = lm;
         H->cheb_c1.assign(nl, std::vector<double>(kChebMaxDeg));
@@ -1777,6 +1828,78 @@ int pamg_estimate_lmax(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* v, pamg_vec* 
         CHECK(lmax_sums(ctx, A->nrows, y->d, A->d_diag, v->d, all_parts != 0, sums));
         if (sums[1] == 0.0 || !std::isfinite(sums[1]))
             return fail(PAMG_E_ARG, "estimate_lmax: step %d: sum (a_ii v_i) v_i = %g (a zero or non-finite iterate)",
+                        k + 1, sums[1]);
+        lam[k] = sums[0] / sums[1];
+    }
+    return PAMG_OK;
+}
+
+// The argument checks the three block entry points share (those of their scalar forms, then the block data).
+static int check_block_op(const pamg_mat* A, const char* what) {
+    if (A->nrows != (A->plan ? A->plan->n_own : A->ncols) || A->interior.pnc || A->interior.rpat)
+        return fail(PAMG_E_ARG, "%s: the operator must be square (%lld rows, %lld own columns)", what,
+                    (long long)A->nrows, (long long)(A->plan ? A->plan->n_own : A->ncols));
+    if (A->bs < 2) return fail(PAMG_E_STATE, "%s: the matrix carries no block data (pamg_mat_set_block_diag)", what);
+    return PAMG_OK;
+}
+
+int pamg_block_jacobi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp, double omega,
+                      int nsweeps) {
+    if (!ctx || !A || !x || !b || !tmp || nsweeps < 0) return fail(PAMG_E_ARG, "block_jacobi: bad args");
+    CHECK(check_block_op(A, "block_jacobi"));
+    CHECK(check_vec_for(A, x, "block_jacobi"));
+    CHECK(check_vec_for(A, tmp, "block_jacobi"));
+    if (b->n_own != A->nrows || tmp == x || b == x || b == tmp)
+        return fail(PAMG_E_ARG, "block_jacobi: size mismatch or aliasing");
+    CHECK(set_device(ctx));
+    double* cur = x->d;
+    double* nxt = tmp->d;
+    for (int k = 0; k < nsweeps; ++k) {
+        CHECK(block_step(ctx, A, pamg::BM_JACOBI, cur, b->d, nullptr, nxt, 0.0, omega));
+        std::swap(cur, nxt);
+    }
+    if (cur != x->d)
+        HIPC(hipMemcpyAsync(x->d, cur, sizeof(double) * x->n_own, hipMemcpyDeviceToDevice, ctx->s_comp));
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_block_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b, pamg_vec* tmp1,
+                         pamg_vec* tmp2, double lmax, double ratio, int degree) {
+    if (!ctx || !A || !x || !b || !tmp1 || !tmp2) return fail(PAMG_E_ARG, "block_chebyshev: NULL");
+    double c1[kChebMaxDeg], c2[kChebMaxDeg];
+    CHECK(pamg_chebyshev_coeffs(lmax, ratio, degree, c1, c2));
+    CHECK(check_block_op(A, "block_chebyshev"));
+    CHECK(check_vec_for(A, x, "block_chebyshev"));
+    CHECK(check_vec_for(A, tmp1, "block_chebyshev"));
+    CHECK(check_vec_for(A, tmp2, "block_chebyshev"));
+    if (b->n_own != A->nrows || tmp1 == x || tmp2 == x || tmp1 == tmp2 || b == x || b == tmp1 || b == tmp2)
+        return fail(PAMG_E_ARG, "block_chebyshev: size mismatch or aliasing");
+    CHECK(set_device(ctx));
+    double* ring[3] = {tmp1->d, tmp2->d, x->d};
+    double* res = nullptr;
+    CHECK(cheb_poly(ctx, A, A->nrows, c1, c2, degree, x->d, b->d, ring, &res, true));
+    if (res != x->d)
+        HIPC(hipMemcpyAsync(x->d, res, sizeof(double) * x->n_own, hipMemcpyDeviceToDevice, ctx->s_comp));
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_estimate_lmax_block(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* v, pamg_vec* y, int steps, int all_parts,
+                             double* lam) {
+    if (!ctx || !A || !v || !y || !lam) return fail(PAMG_E_ARG, "estimate_lmax_block: NULL");
+    if (v == y) return fail(PAMG_E_ARG, "estimate_lmax_block: v and y must differ");
+    if (steps < 1 || steps > 64) return fail(PAMG_E_ARG, "estimate_lmax_block: need 1 <= steps <= 64");
+    CHECK(check_block_op(A, "estimate_lmax_block"));
+    CHECK(check_vec_for(A, v, "estimate_lmax_block"));
+    if (y->n_own != A->nrows) return fail(PAMG_E_ARG, "estimate_lmax_block: output size mismatch");
+    CHECK(set_device(ctx));
+    for (int k = 0; k < steps; ++k) {
+        CHECK(apply(ctx, A, pamg::OP_SPMV, v->d, nullptr, y->d, 0.0));
+        double sums[2] = {0.0, 0.0};
+        CHECK(lmax_sums(ctx, A->nrows, y->d, nullptr, v->d, all_parts != 0, sums, A));
+        if (sums[1] == 0.0 || !std::isfinite(sums[1]))
+            return fail(PAMG_E_ARG, "estimate_lmax_block: step %d: sum (D_b v)_i v_i = %g (a zero or non-finite iterate)",
                         k + 1, sums[1]);
         lam[k] = sums[0] / sums[1];
     }
@@ -1973,7 +2096,8 @@ static int vcycle_raw(pamg_hier* H, double* x, const double* b, int ncycles, boo
     if (pipe_ok(H, ncycles, zero0)) return vcycle_pipe(H, x, b, ncycles);
     // Chebyshev from a given guess: level 0's rings need a fourth vector where exactly one of the two
     // degrees is a multiple of 3 (vcycle_enqueue); allocated before any capture
-    if (H->smoother == PAMG_SMOOTHER_CHEBYSHEV && H->L > 1 && !zero0 && (H->nu1 % 3 == 0) != (H->nu2 % 3 == 0))
+    if ((H->smoother == PAMG_SMOOTHER_CHEBYSHEV || H->smoother == PAMG_SMOOTHER_BLOCK_CHEBYSHEV) && H->L > 1 && !zero0 &&
+        (H->nu1 % 3 == 0) != (H->nu2 % 3 == 0))
         CHECK(ensure_u0(H));
     if (H->use_graph && !H->prof && (!H->gexec || H->g_x != x || H->g_b != b || H->g_zero0 != zero0)) {
         // Capture one cycle (RCCL exchanges included on several parts: RCCL records its

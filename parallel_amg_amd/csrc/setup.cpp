@@ -567,4 +567,91 @@ int pamg_setup_cholinv(const pamg_hcsr* A, double* ainv) {
     return PAMG_OK;
 }
 
+// SPEC §S12: the node blocks D_m of the own rows, their §S5 inverses and rho_b = ||D_b^-1 A||_inf.
+int pamg_setup_block_diag(const pamg_hcsr* A, int64_t row0, int bs, double* blocks, double* inv, double* rho_b) {
+    if (!valid(A) || !blocks || !inv || !rho_b) return fail(PAMG_E_ARG, "block_diag: bad args");
+    if (bs < 2 || bs > 4) return fail(PAMG_E_ARG, "block_diag: block size %d outside 2..4", bs);
+    if (A->nr % bs != 0 || row0 < 0 || row0 % bs != 0)
+        return fail(PAMG_E_ARG, "block_diag: %lld rows from row %lld are not whole blocks of %d", (long long)A->nr,
+                    (long long)row0, bs);
+    const int64_t nb = A->nr / bs;
+    double best = 0.0;
+    int64_t bad = -1;
+#pragma omp parallel for schedule(static) reduction(max : best)
+    for (int64_t m = 0; m < nb; ++m) {
+        const int64_t i0 = m * bs, g0 = row0 + i0;
+        double D[4][4] = {}, L[4][4] = {}, Z[4][4] = {};
+        for (int i = 0; i < bs; ++i)
+            for (int64_t a = A->rp[i0 + i]; a < A->rp[i0 + i + 1]; ++a) {
+                const int64_t j = (int64_t)A->col[a] - g0;
+                if (j >= 0 && j < bs) D[i][j] = A->val[a];
+            }
+        for (int i = 0; i < bs; ++i)
+            for (int j = 0; j < bs; ++j) blocks[(i0 + i) * bs + j] = D[i][j];
+        // §S5 on D_m: Cholesky column by column, then one forward and one back solve per unit vector
+        bool spd = true;
+        for (int j = 0; j < bs && spd; ++j) {
+            double d = D[j][j];
+            for (int k = 0; k < j; ++k) d = d - L[j][k] * L[j][k];
+            if (!(d > 0.0)) { spd = false; break; }
+            L[j][j] = std::sqrt(d);
+            for (int i = j + 1; i < bs; ++i) {
+                double s = D[i][j];
+                for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
+                L[i][j] = s / L[j][j];
+            }
+        }
+        if (!spd) {
+#pragma omp critical(pamg_block_diag_bad)
+            if (bad < 0 || m < bad) bad = m;
+            for (int i = 0; i < bs; ++i)
+                for (int j = 0; j < bs; ++j) inv[(i0 + i) * bs + j] = 0.0;
+            continue;
+        }
+        for (int c = 0; c < bs; ++c) {
+            double y[4];
+            for (int i = 0; i < bs; ++i) {
+                double s = (i == c) ? 1.0 : 0.0;
+                for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+                y[i] = s / L[i][i];
+            }
+            for (int i = bs - 1; i >= 0; --i) {
+                double s = y[i];
+                for (int k = bs - 1; k > i; --k) s = s - L[k][i] * Z[k][c];
+                Z[i][c] = s / L[i][i];
+            }
+        }
+        for (int i = 0; i < bs; ++i)
+            for (int j = 0; j < bs; ++j) inv[(i0 + i) * bs + j] = Z[i][j];
+        // rows of D_m^-1 A: a merge over the block's rows by ascending column
+        int64_t pos[4];
+        double rs[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int j = 0; j < bs; ++j) pos[j] = A->rp[i0 + j];
+        for (;;) {
+            int64_t c = -1;
+            for (int j = 0; j < bs; ++j)
+                if (pos[j] < A->rp[i0 + j + 1] && (c < 0 || A->col[pos[j]] < c)) c = A->col[pos[j]];
+            if (c < 0) break;
+            double ac[4];
+            for (int j = 0; j < bs; ++j) {
+                const bool has = pos[j] < A->rp[i0 + j + 1] && A->col[pos[j]] == c;
+                ac[j] = has ? A->val[pos[j]] : 0.0;
+                if (has) ++pos[j];
+            }
+            for (int i = 0; i < bs; ++i) {
+                double s = 0.0;
+                for (int j = 0; j < bs; ++j) s = s + Z[i][j] * ac[j];
+                rs[i] = rs[i] + std::fabs(s);
+            }
+        }
+        for (int i = 0; i < bs; ++i)
+            if (rs[i] > best) best = rs[i];
+    }
+    if (bad >= 0)
+        return fail(PAMG_E_SETUP, "block_diag: block %lld (rows %lld..%lld) is not positive definite",
+                    (long long)(row0 / bs + bad), (long long)(row0 + bad * bs), (long long)(row0 + bad * bs + bs - 1));
+    *rho_b = best;
+    return PAMG_OK;
+}
+
 }  // extern "C"

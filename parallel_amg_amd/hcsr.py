@@ -191,6 +191,18 @@ def hstack_rows(pieces) -> HCSR:
 MAX_DENSE_COARSE = 16384  # PAMG_MAX_DENSE_COARSE
 
 
+def block_diag(A: HCSR, row0: int, bs: int):
+    """The point blocks of A's rows (global rows row0..; SPEC §S12): ``(blocks, inv, rho_b)`` — two
+    (nrows, bs) arrays, row i holding its bs entries of its node block D_m and of the block's §S5
+    inverse, and rho_b = ||D_b^-1 A||_inf over these rows."""
+    n = A.nrows * max(int(bs), 0)
+    blocks, inv = np.zeros(n, np.float64), np.zeros(n, np.float64)
+    rho = C.c_double()
+    call("pamg_setup_block_diag", A.handle, int(row0), int(bs), blocks.ctypes.data_as(C.c_void_p),
+         inv.ctypes.data_as(C.c_void_p), C.byref(rho))
+    return blocks.reshape(A.nrows, int(bs)), inv.reshape(A.nrows, int(bs)), rho.value
+
+
 def cholinv(A: HCSR) -> np.ndarray:
     """Column-major inverse (SPEC §S5) as a flat array of n*n."""
     if A.nrows > MAX_DENSE_COARSE:  # checked before allocating n*n doubles (pamg.h)

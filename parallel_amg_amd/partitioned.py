@@ -368,6 +368,24 @@ class PSparseMatrix:
         sb = C.c_int64()
         call("pamg_mat_stream_bytes", h, C.byref(sb))
         self.stream_bytes = sb.value  # matrix bytes one row operation reads (uploaded layout)
+        self.block_size = 1
+
+    def set_block_diag(self, bs: int = 1, blocks=None, inv=None):
+        """Attach the point blocks of the own rows and their inverses (``hcsr.block_diag``'s arrays;
+        SPEC §S12) for the block smoothers, or remove them (``bs = 1`` or no arrays). A hierarchy
+        that uses the matrix must be told: call ``AMGSolver.set_smoother`` again."""
+        if bs == 1 or blocks is None or inv is None:
+            call("pamg_mat_set_block_diag", self.ctx.handle, self._h, int(bs), None, None)
+        else:
+            bl = np.ascontiguousarray(blocks, np.float64).reshape(-1)
+            iv = np.ascontiguousarray(inv, np.float64).reshape(-1)
+            if bl.size != self.nrows * int(bs) or iv.size != bl.size:
+                raise ValueError(f"set_block_diag: blocks and inv need {self.nrows} x {bs} entries")
+            call("pamg_mat_set_block_diag", self.ctx.handle, self._h, int(bs), bl.ctypes.data_as(C.c_void_p),
+                 iv.ctypes.data_as(C.c_void_p))
+        out = C.c_int()
+        call("pamg_mat_block_size", self._h, C.byref(out))
+        self.block_size = out.value
 
     @property
     def handle(self):
@@ -425,6 +443,30 @@ def estimate_lmax(A: PSparseMatrix, v: PVector, y: PVector, steps: int = 10, all
     parts of the context (collective), or over this part only for a level held whole on every part."""
     lam = np.zeros(max(int(steps), 1))
     call("pamg_estimate_lmax", A.ctx.handle, A.handle, v.handle, y.handle, int(steps), int(bool(all_parts)), ptr(lam))
+    return lam
+
+
+def block_jacobi(x: PVector, A: PSparseMatrix, b: PVector, tmp: PVector, omega: float, nsweeps: int = 1):
+    """``nsweeps`` point-block Jacobi sweeps x += omega D_b^-1 (b - A x) (SPEC §S12; result in x) on a
+    matrix with block data (``A.set_block_diag``)."""
+    call("pamg_block_jacobi", A.ctx.handle, A.handle, x.handle, b.handle, tmp.handle, float(omega), nsweeps)
+    return x
+
+
+def block_chebyshev(x: PVector, A: PSparseMatrix, b: PVector, tmp1: PVector, tmp2: PVector, lmax: float,
+                    ratio: float = 4.0, degree: int = 2) -> PVector:
+    """``chebyshev`` with D_b^-1 for D^-1 (SPEC §S12): the polynomial of D_b^-1 A over [lmax / ratio, lmax]."""
+    call("pamg_block_chebyshev", A.ctx.handle, A.handle, x.handle, b.handle, tmp1.handle, tmp2.handle, float(lmax),
+         float(ratio), int(degree))
+    return x
+
+
+def estimate_lmax_block(A: PSparseMatrix, v: PVector, y: PVector, steps: int = 10,
+                        all_parts: bool = True) -> np.ndarray:
+    """``estimate_lmax`` for lambda_max(D_b^-1 A) (SPEC §S12): v <- D_b^-1 y, denominators (D_b v).v."""
+    lam = np.zeros(max(int(steps), 1))
+    call("pamg_estimate_lmax_block", A.ctx.handle, A.handle, v.handle, y.handle, int(steps), int(bool(all_parts)),
+         ptr(lam))
     return lam
 
 
