@@ -184,6 +184,19 @@ int pamg_mat_upload_perm(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, cons
                          const void* col, int col_is_64, const double* val, int index_base,
                          const pamg_plan* col_plan, const int64_t* row_perm,
                          const int64_t* col_perm, pamg_mat** out);
+/* The same upload for a square node-major operator of block size bs (row bs m + d is unknown d of node
+ * m): where the bs rows of every node store the same block columns, every touched bs x bs block whole
+ * (explicit zeros stored), no row has a ghost column and every diagonal entry is nonzero, the rows go
+ * into the block-row layout (bsr: a sliced ELL over block rows, one column index per block — 8 + 4 / bs^2
+ * bytes per nonzero — and one x gather of bs adjacent doubles per block; pamg_mat_layout out[9] bit 15).
+ * Every row operation keeps its bits (SPEC §S3: a lane walks its node's blocks in stored order). A matrix
+ * that does not qualify — partial blocks, node rows with different block columns, a part of several with
+ * ghost columns — uploads successfully in the layouts pamg_mat_upload gives it; bit 15 tells which
+ * happened. bs = 1 is pamg_mat_upload. PAMG_E_ARG for bs outside 1..4 and, with bs > 1, for nrows % bs
+ * != 0 or an operator that is not square. There is no permuted variant: renumber the nodes before setup. */
+int pamg_mat_upload_blocked(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, const int64_t* rowptr,
+                            const void* col, int col_is_64, const double* val, int index_base,
+                            const pamg_plan* col_plan, int bs, pamg_mat** out);
 int pamg_mat_destroy(pamg_mat* A);
 int pamg_mat_info(const pamg_mat* A, int64_t* nrows, int64_t* ncols_local, int64_t* nnz);
 /* Bytes of matrix data one row operation streams in the layout chosen at upload: 8 B values +
@@ -218,7 +231,9 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes);
  * grid); bit 12: with bit 10, the rows hold 16-bit combination ids instead of 64-bit records
  * (pnc_compact; out[4] = the combinations); bit 13: with bit 9, one index byte per nonzero names an
  * (offset, value) pair of the group (ell_pair); bit 14: with bit 10, the grid cuts into whole tiles
- * and "pnc" = 1 launches the tiled march (k_rows_pnct) for it (out[8] is the grid of either march). */
+ * and "pnc" = 1 launches the tiled march (k_rows_pnct) for it (out[8] is the grid of either march);
+ * bit 15: the set runs in the block-row layout (bsr; pamg_mat_upload_blocked: then out[3] = the block
+ * size, out[4] = the padded block slots, out[8] = the kernel's grid). */
 int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
 /* The windowed sliced-ELL layout of a matrix (ell_xwin; with pamg_mat_layout bits 9 and 13): out[0]
  * 1 where the matrix runs in it (else all 0), out[1] the groups whose x window is staged in LDS,
@@ -234,7 +249,10 @@ int pamg_mat_ell_window(const pamg_mat* A, int out[16]);
  * each: row i's bs entries of its node block D_m, and of D_m^-1), uploaded beside the diagonal. bs = 1
  * or a NULL array removes them. PAMG_E_ARG for bs outside 1..4, an operator that is not square, or
  * nrows % bs != 0; PAMG_E_STATE for a matrix uploaded with a permutation (pamg_mat_upload_perm).
- * Nothing else about the matrix changes: every existing call keeps its bits. A hierarchy that
+ * Nothing else about the matrix changes: every existing call keeps its bits. On a matrix in the block-row
+ * layout (pamg_mat_upload_blocked, bit 15) whose block size is bs, a point-block sweep (pamg_block_jacobi,
+ * pamg_block_chebyshev, the block smoothers of a hierarchy) is one pass over the matrix instead of a
+ * residual pass and a block pass, with the same bits. A hierarchy that
  * references the matrix must be told (pamg_hier_set_smoother) after the block data changes. */
 int pamg_mat_set_block_diag(pamg_ctx* ctx, pamg_mat* A, int bs, const double* blocks, const double* inv);
 /* The block size set above (1: no block data). */

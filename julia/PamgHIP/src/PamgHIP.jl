@@ -354,25 +354,37 @@ mutable struct DeviceMatrix
 end
 """
     DeviceMatrix(ctx, rowptr, col, val, ncols_local; plan = nothing, index_base = 1,
-                 row_perm = nothing, col_perm = nothing)
+                 row_perm = nothing, col_perm = nothing, block_size = 1)
 
 One part's own rows in CSR with LOCAL column ids (own columns first, then the plan's ghost
 slots), each row in ascending global column order (SPEC §S1). Int64 or Int32 columns, 1- or
 0-based (`index_base`). The library copies the arrays. `row_perm` / `col_perm` (1-based, one
 part): the locality permutation of pamg_mat_upload_perm — device row i is row row_perm[i],
 device own column k is own column col_perm[k]; rows keep their storage order (same bits).
+`block_size` > 1 (pamg_mat_upload_blocked; not with a permutation): a square node-major operator of
+that many unknowns per node takes the block-row layout where every node's rows store the same whole
+blocks and no row has a ghost column (`layout(A).bsr`; same bits), else the layouts of a plain upload.
 """
 function DeviceMatrix(ctx::Context, rowptr::AbstractVector{<:Integer}, col::AbstractVector{<:Integer},
                       val::AbstractVector{<:Real}, ncols_local::Integer;
                       plan::Union{Nothing,ExchangePlan} = nothing, index_base::Integer = 1,
                       row_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing,
-                      col_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing)
+                      col_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing,
+                      block_size::Integer = 1)
+    block_size != 1 && (row_perm !== nothing || col_perm !== nothing) &&
+        throw(ArgumentError("DeviceMatrix: block_size > 1 cannot be combined with row_perm / col_perm"))
     rp = Vector{Int64}(rowptr)
     c = eltype(col) == Int32 ? Vector{Int32}(col) : Vector{Int64}(col)
     is64 = eltype(c) == Int64 ? Cint(1) : Cint(0)
     v = Vector{Float64}(val)
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    if row_perm === nothing && col_perm === nothing
+    if block_size != 1
+        check(ccall((:pamg_mat_upload_blocked, libpamg), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Cvoid}, Cint,
+                     Ptr{Ptr{Cvoid}}),
+                    ctx.h, length(rp) - 1, ncols_local, rp, c, is64, v, index_base,
+                    plan === nothing ? C_NULL : plan.h, block_size, h))
+    elseif row_perm === nothing && col_perm === nothing
         check(ccall((:pamg_mat_upload, libpamg), Cint,
                     (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}),
                     ctx.h, length(rp) - 1, ncols_local, rp, c, is64, v, index_base,
@@ -415,7 +427,7 @@ function layout(A::DeviceMatrix, set::Integer = 0)
     check(ccall((:pamg_mat_layout, libpamg), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), A.h, set, out))
     (c24 = out[1] != 0, vd = out[2] != 0, rl8 = out[3] != 0, cd = Int(out[4]), cd_offsets = Int(out[5]),
      tm = out[6] != 0, tm_rs = Int(out[7]), tile_nnz = Int(out[8]), tiles = Int(out[9]), anchored = (out[10] & 1) != 0, per_tile = (out[10] & 2) != 0,
-     x_stage = (out[10] & 4) != 0)
+     x_stage = (out[10] & 4) != 0, bsr = (out[10] & 32768) != 0)
 end
 "The windowed sliced-ELL layout of a matrix (`ell_xwin`): whether it runs in it, its windowed and gathering groups, the largest window."
 function ell_window(A::DeviceMatrix)

@@ -79,6 +79,7 @@ SIGNATURES = {
     "pamg_exchange_end": [vp, vp, vp],
     "pamg_mat_upload": [vp, i64, i64, vp, vp, i32, vp, i32, vp, pvp],
     "pamg_mat_upload_perm": [vp, i64, i64, vp, vp, i32, vp, i32, vp, vp, vp, pvp],
+    "pamg_mat_upload_blocked": [vp, i64, i64, vp, vp, i32, vp, i32, vp, i32, pvp],
     "pamg_mat_destroy": [vp],
     "pamg_mat_info": [vp, pi64, pi64, pi64],
     "pamg_mat_stream_bytes": [vp, pi64],
@@ -233,7 +234,8 @@ def layout_of(M, part_set: int = 0) -> dict:
             "jr_fused": bool(out[9] & 32), "tm_vd": bool(out[9] & 64), "sym_vd": bool(out[9] & 128),
             "ell": bool(out[9] & 512), "pnc": bool(out[9] & 1024),
             "rpat": bool(out[9] & 2048), "pnc_compact": bool(out[9] & 4096),
-            "ell_pair": bool(out[9] & 8192), "pnc_tiled": bool(out[9] & 16384)}  # (ell_xwin*: pamg_mat_ell_window)
+            "ell_pair": bool(out[9] & 8192), "pnc_tiled": bool(out[9] & 16384),
+            "bsr": bool(out[9] & 32768)}  # (ell_xwin*: pamg_mat_ell_window)
 
 
 def last_error() -> str:

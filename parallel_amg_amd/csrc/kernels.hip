@@ -3014,9 +3014,14 @@ void launch_rpat(const pamg_mat& A, const double* x, const double* b, double* y,
     go(k_rows_rpat<OP, 8>);
 }
 
+// (the block-row kernel and its launcher stand after every other kernel of this unit)
+template <int OP, int FUSE>
+void launch_bsr(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s, Cheb ch);
+
 template <int OP>
 void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const double* b,
                     double* y, double omega, hipStream_t s, Cheb ch = Cheb{}) {
+    if (ts.bsr) launch_bsr<OP, 0>(A, x, b, y, omega, s, ch);
     if (ts.sym) launch_sym<OP>(A, x, b, y, omega, s, ch);
     if (ts.ell) {
         const EllSet& E = A.ell;
@@ -3141,7 +3146,133 @@ __global__ void k_pcg_dir(int64_t n, const PcgScalars* S, const double* __restri
         p[i] = u + v;
     }
 }
+
+// ------------------------------------------------------------------ block-row layout (pamg::BsrSet)
+// One lane per block row (node), one slice of kEllW block rows per wave, kBsrSlices slices per workgroup.
+// A lane walks its node's block slots in order; per slot it loads the block column, the BS entries of x
+// the block reads (adjacent doubles; 16-byte loads for BS 2 and 4 where x is 16-byte aligned) and the
+// block's BS^2 values (each load contiguous over the wave), and adds s_d = s_d + v_de x_e for e = 0 ..
+// BS - 1 into one accumulator per row d of the node — row BS m + d's stored order, each product and each
+// add rounded once (SPEC §S3). A padded slot (column -1) is skipped whole. The lane then holds the node's
+// BS row sums: the scalar epilogues run per d, and the fused forms (FUSE 1: block Jacobi, 2: the block
+// Chebyshev step; OP_RESID) apply D_m^-1 from the lane's BS^2 entries of d_binv in registers — k_block_update's
+// roundings in its order, with no second pass and no LDS. No barrier: a wave past the last slice leaves.
+template <int BS>
+__device__ __forceinline__ void bsr_load_x(const double* __restrict__ x, int c, bool x16, double (&xe)[BS]) {
+    const double* p = x + (int64_t)c * BS;
+    if constexpr (BS == 3) {
+        xe[0] = p[0];
+        xe[1] = p[1];
+        xe[2] = p[2];
+    } else {
+        if (x16) {
+#pragma unroll
+            for (int e = 0; e < BS; e += 2) {
+                const double2 v = *reinterpret_cast<const double2*>(p + e);
+                xe[e] = v.x;
+                xe[e + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < BS; ++e) xe[e] = p[e];
+        }
+    }
+}
+
+template <int BS, int OP, int FUSE>
+__global__ __launch_bounds__(kBlock) void k_rows_bsr(int nb, int ns, const int64_t* __restrict__ soff,
+                                                     const int* __restrict__ bcol, const double* __restrict__ val,
+                                                     const double* __restrict__ diag,
+                                                     const double* __restrict__ binv, int x16,
+                                                     const double* __restrict__ x, const double* __restrict__ b,
+                                                     double* __restrict__ y, double omega, double c1,
+                                                     const double* __restrict__ xold) {
+    const int lane = threadIdx.x & (kEllW - 1);
+    const int sl = blockIdx.x * kBsrSlices + (threadIdx.x >> 6);
+    if (sl >= ns) return;
+    const int64_t k0 = soff[sl], k1 = soff[sl + 1];
+    const int m = sl * kEllW + lane;
+    double s[BS];
+#pragma unroll
+    for (int d = 0; d < BS; ++d) s[d] = 0.0;
+    const int* cp = bcol + k0 * kEllW + lane;
+    const double* vp = val + k0 * (BS * BS) * kEllW + lane;
+    for (int64_t k = k0; k < k1; ++k, cp += kEllW, vp += BS * BS * kEllW) {
+        const int c = *cp;
+        if (c < 0) continue;
+        double xe[BS], v[BS * BS];
+        bsr_load_x<BS>(x, c, x16 != 0, xe);
+#pragma unroll
+        for (int j = 0; j < BS * BS; ++j) v[j] = vp[j * kEllW];
+#pragma unroll
+        for (int d = 0; d < BS; ++d) {
+#pragma unroll
+            for (int e = 0; e < BS; ++e) {
+                const double p = v[d * BS + e] * xe[e];
+                s[d] = s[d] + p;
+            }
+        }
+    }
+    if (m >= nb) return;
+    const int64_t r0 = (int64_t)m * BS;
+    if constexpr (FUSE == 0) {
+#pragma unroll
+        for (int d = 0; d < BS; ++d) {
+            double dg = 1.0;
+            if constexpr (kDiagOp<OP>) dg = diag[r0 + d];
+            epilogue<OP>((int)(r0 + d), s[d], x, b, y, omega, dg, c1, xold);
+        }
+    } else {
+        double u[BS];
+#pragma unroll
+        for (int d = 0; d < BS; ++d) u[d] = b[r0 + d] - s[d];
+        const double* di = binv + r0 * BS;
+#pragma unroll
+        for (int d = 0; d < BS; ++d) {
+            double w = 0.0;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) {
+                const double p = di[d * BS + j] * u[j];
+                w = w + p;
+            }
+            const int64_t r = r0 + d;
+            if constexpr (FUSE == 1) {
+                const double vv = omega * w;
+                y[r] = x[r] + vv;
+            } else {
+                const double xi = x[r];
+                const double vv = omega * w;
+                const double e = xi - (xold ? xold[r] : 0.0);
+                const double q = c1 * e;
+                const double t = q + vv;
+                y[r] = xi + t;
+            }
+        }
+    }
+}
+
+template <int OP, int FUSE>
+void launch_bsr(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s, Cheb ch) {
+    const BsrSet& B = A.bsr;
+    if (B.nb <= 0) return;
+    const int x16 = (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? 1 : 0;
+    auto go = [&](auto kern) {
+        kern<<<B.grid, kBlock, 0, s>>>((int)B.nb, (int)B.nslices, B.d_soff, B.d_bcol, B.d_val, A.d_diag, A.d_binv, x16,
+                                       x, b, y, omega, ch.c1, ch.xold);
+    };
+    switch (B.bs) {
+        case 2: go(k_rows_bsr<2, OP, FUSE>); break;
+        case 3: go(k_rows_bsr<3, OP, FUSE>); break;
+        default: go(k_rows_bsr<4, OP, FUSE>); break;
+    }
+}
 }  // namespace
+
+void launch_bsr_block(const pamg_mat& A, int mode, const double* x, const double* b, const double* xold, double* y,
+                      double c1, double c2, hipStream_t s) {
+    if (mode == BM_JACOBI) launch_bsr<OP_RESID, 1>(A, x, b, y, c2, s, Cheb{});
+    else launch_bsr<OP_RESID, 2>(A, x, b, y, c2, s, Cheb{c1, xold});
+}
 
 void launch_sym_tb(const pamg_mat& A, const TbArgs& ta, hipStream_t s) {
     SymDia sd = A.sym;

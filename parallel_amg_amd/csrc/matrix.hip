@@ -1,6 +1,6 @@
 // matrix.hip — from a caller's CSR arrays to a finished pamg_mat: the threaded host passes and
 // staged copies of the upload, the detector and builder of every layout family (sym, rpat, ell,
-// pnc, tiles) with its four contract functions, and the pamg_mat_* entry points of include/pamg.h
+// pnc, bsr, tiles) with its four contract functions, and the pamg_mat_* entry points of include/pamg.h
 // that drive them. The rest of the runtime (runtime.hip) reaches this unit through those entry
 // points only; everything else here is file-local.
 #include <algorithm>
@@ -270,6 +270,7 @@ struct Upload {
     const std::vector<int>& bnd;     // the rows with ghost columns (always tiles)
     const std::function<int64_t()>& band;  // the banded tile order's row distance, computed on first use
     UploadTrace& tr;
+    int bs = 1;                      // > 1: uploaded through pamg_mat_upload_blocked (bsr_try)
 };
 // Every family provides four functions. X_try holds the family's eligibility rule and its
 // builder: where it takes the rows it sets its TileSet flag on A->interior and clears
@@ -1670,6 +1671,104 @@ void pnc_free(pamg::PncSet& P) {
     P = pamg::PncSet{};
 }
 
+// ------------------------------------------------------------------ bsr
+
+// Block-row layout (pamg::BsrSet, k_rows_bsr) of a matrix uploaded through pamg_mat_upload_blocked, when it
+// qualifies: the bs rows of every node store the same block columns c_0 < c_1 < ..., row bs m + d as the
+// entries bs c_0, bs c_0 + 1, ..., bs c_0 + bs - 1, bs c_1, ... in that storage order — every touched block
+// whole, and the kernel's walk "blocks in order, e = 0 .. bs - 1 inside" the row's stored order (SPEC §S3).
+// Otherwise nothing is built.
+int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs) {
+    using pamg::kEllW;
+    pamg_ctx* ctx = A->ctx;
+    const int64_t nb = A->nrows / bs, ns = (nb + kEllW - 1) / kEllW;
+    std::atomic<bool> ok{true};
+    par_for(nb, [&](int64_t a, int64_t b) {
+        for (int64_t m = a; m < b && ok.load(std::memory_order_relaxed); ++m) {
+            const int64_t k0 = rp[m * bs], len = rp[m * bs + 1] - k0;
+            bool good = len % bs == 0;
+            for (int d = 0; d < bs && good; ++d) good = rp[m * bs + d + 1] - rp[m * bs + d] == len;
+            for (int64_t j = 0; j < len && good; j += bs) {
+                const int c0 = ci[k0 + j];
+                good = c0 % bs == 0 && (j == 0 || c0 > ci[k0 + j - bs]);
+                for (int d = 0; d < bs && good; ++d)
+                    for (int e = 0; e < bs && good; ++e) good = ci[rp[m * bs + d] + j + e] == c0 + e;
+            }
+            if (!good) ok = false;
+        }
+    });
+    if (!ok) return PAMG_OK;
+    pamg::BsrSet& B = A->bsr;
+    std::vector<int64_t> soff(ns + 1, 0);
+    for (int64_t s = 0; s < ns; ++s) {
+        int64_t w = 0;
+        for (int64_t m = s * kEllW; m < std::min(nb, (s + 1) * kEllW); ++m)
+            w = std::max(w, (rp[m * bs + 1] - rp[m * bs]) / bs);
+        soff[s + 1] = soff[s] + w;
+    }
+    const int64_t slots = soff[ns] * kEllW, b2 = (int64_t)bs * bs;
+    if (slots >= INT32_MAX) return PAMG_OK;  // (pamg_mat_layout reports the slots as an int)
+    std::vector<int> bcol((size_t)slots, -1);
+    std::vector<double> bval((size_t)(slots * b2), 0.0);
+    par_for(nb, [&](int64_t a, int64_t b) {
+        for (int64_t m = a; m < b; ++m) {
+            const int64_t s = m / kEllW, l = m % kEllW, nblk = (rp[m * bs + 1] - rp[m * bs]) / bs;
+            for (int64_t k = 0; k < nblk; ++k) {
+                bcol[(soff[s] + k) * kEllW + l] = ci[rp[m * bs] + k * bs] / bs;
+                for (int d = 0; d < bs; ++d)
+                    for (int e = 0; e < bs; ++e)
+                        bval[((soff[s] + k) * b2 + d * bs + e) * kEllW + l] = val[rp[m * bs + d] + k * bs + e];
+            }
+        }
+    });
+    CHECK(dalloc(&B.d_soff, ns + 1));
+    CHECK(dalloc(&B.d_bcol, std::max<int64_t>(slots, 1)));
+    CHECK(dalloc(&B.d_val, std::max<int64_t>(slots * b2, 1)));
+    CHECK(h2d(ctx, B.d_soff, soff.data(), sizeof(int64_t) * (ns + 1)));
+    CHECK(h2d(ctx, B.d_bcol, bcol.data(), sizeof(int) * bcol.size()));
+    CHECK(h2d(ctx, B.d_val, bval.data(), sizeof(double) * bval.size()));
+    B.bs = bs;
+    B.nb = nb;
+    B.nslices = ns;
+    B.slots = slots;
+    B.grid = (int)((ns + pamg::kBsrSlices - 1) / pamg::kBsrSlices);
+    A->interior.bsr = true;
+    return PAMG_OK;
+}
+
+// a square operator with a nonzero diagonal in every row and no ghost column, in whole nodes
+int bsr_try(Upload& u) {
+    pamg_mat* A = u.A;
+    if (u.bs > 1 && u.n_own_cols == A->nrows && u.has_all_diag && u.bnd.empty() && A->nrows > 0 &&
+        A->nrows % u.bs == 0) {
+        CHECK(build_bsr(A, u.rp, u.ci, u.val, u.bs));
+        if (A->interior.bsr) u.inner.clear();  // the rows run in k_rows_bsr, not in tiles
+        u.tr.mark("bsr");
+    }
+    return PAMG_OK;
+}
+
+// the padded stream: a column and bs^2 values per block slot, the slice offsets
+int64_t bsr_bytes(const pamg_mat* A) {
+    if (!A->interior.bsr) return 0;
+    return A->bsr.slots * (4 + 8 * (int64_t)A->bsr.bs * A->bsr.bs) + 8 * (A->bsr.nslices + 1);
+}
+
+void bsr_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
+    if (!t.bsr) return;
+    out[3] = A->bsr.bs;  // the block size, the padded block slots, k_rows_bsr's grid
+    out[4] = (int)A->bsr.slots;
+    out[8] = A->bsr.grid;
+    out[9] |= 32768;
+}
+
+void bsr_free(pamg::BsrSet& B) {
+    dfree(B.d_soff);
+    dfree(B.d_bcol);
+    dfree(B.d_val);
+    B = pamg::BsrSet{};
+}
+
 // ------------------------------------------------------------------ tiles (every row no other family took)
 
 // tile_order 1 (banded XCD-blocked order) for a square matrix of half-bandwidth `band`:
@@ -2428,7 +2527,7 @@ int tiles_try(Upload& u) {
 int64_t tiles_bytes(const pamg_mat* A) {
     int64_t sum = 0;
     for (const pamg::TileSet* t : {&A->interior, &A->boundary}) {
-        if (t->sym || t->ell || t->pnc || t->rpat) continue;  // counted by their families
+        if (t->sym || t->ell || t->pnc || t->rpat || t->bsr) continue;  // counted by their families
         const int64_t ns = t->n_short, nz = t->nnz_short;
         int64_t b = 8 * (int64_t)t->n_long + 12 * t->nnz_long;
         const bool base = t->c24 && !t->cd;
@@ -2489,15 +2588,10 @@ void tiles_free(pamg::TileSet& ts) {
     ts.n_short = ts.n_long = 0;
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------ C-ABI: pamg_mat_*
-
-extern "C" {
-
-int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr,
-                    const void* col, int col_is_64, const double* val, int index_base,
-                    const pamg_plan* plan, pamg_mat** out) {
+// pamg_mat_upload (bs = 1) and pamg_mat_upload_blocked (bs > 1, its arguments checked): the block-row
+// family is tried first for the latter alone; where it declines the matrix goes on exactly as bs = 1 does
+int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr, const void* col, int col_is_64,
+               const double* val, int index_base, const pamg_plan* plan, int bs, pamg_mat** out) {
     if (!ctx || !out || nrows < 0 || ncols < 0 || !rowptr || (index_base != 0 && index_base != 1))
         return fail(PAMG_E_ARG, "mat_upload: bad args");
     const int64_t nnz = rowptr[nrows] - index_base;
@@ -2632,11 +2726,14 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
     };
     // the layout families in their fixed order: each takes the interior rows left (and clears the
     // list) or declines
-    Upload u{A.get(), rp, ci, val, n_own_cols, has_all_diag, inner, bnd, get_band, tr};
-    CHECK(sym_try(u));
-    CHECK(rpat_try(u));
-    CHECK(ell_try(u));
-    CHECK(pnc_try(u));
+    Upload u{A.get(), rp, ci, val, n_own_cols, has_all_diag, inner, bnd, get_band, tr, bs};
+    CHECK(bsr_try(u));
+    if (!A->interior.bsr) {
+        CHECK(sym_try(u));
+        CHECK(rpat_try(u));
+        CHECK(ell_try(u));
+        CHECK(pnc_try(u));
+    }
     // the CSR copies: read by the tile and long-row kernels only, so not uploaded when every row
     // runs in the symmetric, ELL or neighbour-coded layout (the 512^3 A0, A1, R0, P0: 29 GB less)
     if (!inner.empty() || !bnd.empty()) {
@@ -2660,9 +2757,36 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
     CHECK(tiles_try(u));
     // the bytes one apply streams: every family's share + the closing pointer
     A->stream_bytes = 4 + sym_bytes(A.get()) + ell_bytes(A.get()) + pnc_bytes(A.get()) + rpat_bytes(A.get()) +
-                      tiles_bytes(A.get());
+                      bsr_bytes(A.get()) + tiles_bytes(A.get());
     *out = A.release();
     return PAMG_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C-ABI: pamg_mat_*
+
+extern "C" {
+
+int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr,
+                    const void* col, int col_is_64, const double* val, int index_base,
+                    const pamg_plan* plan, pamg_mat** out) {
+    return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, 1, out);
+}
+
+int pamg_mat_upload_blocked(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr,
+                            const void* col, int col_is_64, const double* val, int index_base,
+                            const pamg_plan* plan, int bs, pamg_mat** out) {
+    if (bs < 1 || bs > 4) return fail(PAMG_E_ARG, "mat_upload_blocked: block size %d outside 1..4", bs);
+    if (bs > 1 && ctx && nrows >= 0 && ncols >= 0) {
+        const int64_t n_own_cols = plan ? plan->n_own : ncols;
+        if (nrows != n_own_cols)
+            return fail(PAMG_E_ARG, "mat_upload_blocked: the operator must be square (%lld rows, %lld own columns)",
+                        (long long)nrows, (long long)n_own_cols);
+        if (nrows % bs != 0)
+            return fail(PAMG_E_ARG, "mat_upload_blocked: %lld rows are not whole blocks of %d", (long long)nrows, bs);
+    }
+    return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, bs, out);
 }
 
 // Locality permutation inside the device layout: device row i = caller row row_perm[i], own
@@ -2802,6 +2926,7 @@ int pamg_mat_destroy(pamg_mat* A) {
     ell_free(A->ell);
     pnc_free(A->pnc);
     rpat_free(A->rpat);
+    bsr_free(A->bsr);
     pamg_ctx* owner = A->ctx;
     delete A;
     ctx_unref(owner);
@@ -2830,6 +2955,7 @@ int pamg_mat_layout(const pamg_mat* A, int set, int out[10]) {
     rpat_report(A, t, out);
     pnc_report(A, t, out);
     sym_report(A, t, out);
+    bsr_report(A, t, out);
     return PAMG_OK;
 }
 

@@ -108,6 +108,9 @@ struct TileSet {
     // pattern-dictionary rows (pamg_mat::rpat; the whole interior set of a restriction): the rows run in
     // k_rows_rpat instead of tiles
     bool rpat = false;
+    // block-row layout (pamg_mat::bsr; the whole of a square node-major operator uploaded through
+    // pamg_mat_upload_blocked): the rows run in k_rows_bsr instead of tiles
+    bool bsr = false;
     int max_short_len = 0;    // longest row in a short tile
     int64_t rows_short = 0;   // rows covered by the short tiles
     int64_t nnz_short = 0, nnz_long = 0;  // nonzeros covered by the tiles / the long rows
@@ -311,6 +314,27 @@ struct RpatSet {
     int npat = 0, nent = 0, nval = 0;
 };
 
+// Block-row layout (pamg_mat_upload_blocked; k_rows_bsr): a square one-part operator in node-major order
+// whose rows bs m .. bs m + bs - 1 (node m) store the same block columns, every touched bs x bs block
+// whole (explicit zeros stored) and each row's entries in ascending column order. A sliced ELL over
+// block rows in natural order: slice s holds the kEllW block rows from kEllW s, one per lane of a wave,
+// padded to the slice's own width (the most blocks of any of its rows); its slots start at block slot
+// d_soff[s] (64-bit) and number d_soff[s + 1] - d_soff[s]. Slot k of slice s, lane l: the block column at
+// d_bcol[(d_soff[s] + k) * kEllW + l] (-1: padding — skipped, no x read, no product, SPEC §S3), the
+// block's entry (d, e) at d_val[((d_soff[s] + k) * bs * bs + d * bs + e) * kEllW + l]. One column index per
+// block: 8 + 4 / bs^2 bytes per stored nonzero; x is gathered once per block as bs adjacent doubles; a
+// lane holds its node's bs row sums in registers (the fused block smoothers of SPEC §S12).
+constexpr int kBsrSlices = kBlock / kEllW;  // slices (waves) per workgroup
+struct BsrSet {
+    int bs = 0;
+    int64_t nb = 0, nslices = 0;  // block rows, slices
+    int64_t slots = 0;            // padded block slots: d_soff[nslices] * kEllW
+    int64_t* d_soff = nullptr;    // nslices + 1
+    int* d_bcol = nullptr;        // slots
+    double* d_val = nullptr;      // slots * bs * bs
+    int grid = 0;                 // workgroups of k_rows_bsr
+};
+
 struct SymDia {
     int nu = 0;                     // upper offset classes
     int off[kSymMaxU] = {};         // ascending positive offsets
@@ -428,6 +452,7 @@ struct pamg_mat {
     pamg::EllSet ell;        // the interior set's sliced-ELL layout (TileSet::ell)
     pamg::PncSet pnc;        // the neighbour-coded prolongation layout (TileSet::pnc)
     pamg::RpatSet rpat;      // the pattern-dictionary restriction layout (TileSet::rpat)
+    pamg::BsrSet bsr;        // the block-row layout (TileSet::bsr)
     int64_t stream_bytes = 0;  // matrix bytes one apply reads (values, columns, row pointers, tiles)
 };
 
@@ -488,6 +513,15 @@ void launch_lmax_step(int64_t n, const double* y, const double* diag, double* v,
 enum BlockMode : int { BM_JACOBI = 0, BM_ZERO = 1, BM_CHEB = 2, BM_SOLVE = 3 };
 void launch_block_update(const pamg_mat& A, int mode, const double* u, const double* x, const double* xold, double* y,
                          double c1, double c2, hipStream_t s);
+// SPEC §S12, a whole point-block sweep in one launch on a block-row operator (A.interior.bsr, A.bs ==
+// A.bsr.bs, block data attached; bsr_fused below): the lane that holds node m's row sums forms u = b - s
+// and w = D_m^-1 u in registers, then BM_JACOBI or BM_CHEB as launch_block_update writes them — the same
+// roundings in the same order, so the bits of the two passes. y differs from x and xold.
+inline bool bsr_fused(const pamg_mat& A) {
+    return A.interior.bsr && A.bs > 1 && A.bs == A.bsr.bs && A.d_binv != nullptr;
+}
+void launch_bsr_block(const pamg_mat& A, int mode, const double* x, const double* b, const double* xold, double* y,
+                      double c1, double c2, hipStream_t s);
 // SPEC §S12 estimate step after y = A v: out[0] = v.y, out[1] = (D_b v).v (launch_lmax_step's order and
 // trees), then v <- D_b^-1 y in a pass of its own. partials holds 2 np doubles.
 void launch_lmax_step_block(const pamg_mat& A, const double* y, double* v, double* partials, int np, double* out,

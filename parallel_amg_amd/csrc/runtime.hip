@@ -358,13 +358,17 @@ int apply(pamg_ctx* ctx, const pamg_mat* A, int op, double* x, const double* b, 
 
 // One smoothing step in point-block form (SPEC §S12) on an operator that carries block data: the residual
 // b - A x of the layout's own OP_RESID into y (x's ghosts exchanged by apply), then the block pass over
-// the own rows turns y into the new iterate in place. BM_ZERO reads b alone (no row sums); y differs
-// from x and xold.
+// the own rows turns y into the new iterate in place — or, where the operator's rows are in the block-row
+// layout with this block size, one fused launch with the same bits. BM_ZERO reads b alone (no row sums); y
+// differs from x and xold.
 int block_step(pamg_ctx* ctx, const pamg_mat* A, int mode, double* x, const double* b, const double* xold, double* y,
                double c1, double c2) {
     hipStream_t s = ctx->s_comp;
     if (mode == pamg::BM_ZERO) {
         pamg::launch_block_update(*A, mode, b, nullptr, nullptr, y, 0.0, c2, s);
+    } else if (pamg::bsr_fused(*A) && (mode == pamg::BM_JACOBI || mode == pamg::BM_CHEB)) {
+        // a block-row operator (no ghost column, so no exchange): the whole sweep in one launch
+        pamg::launch_bsr_block(*A, mode, x, b, xold, y, c1, c2, s);
     } else {
         CHECK(apply(ctx, A, pamg::OP_RESID, x, b, y, 0.0));
         pamg::launch_block_update(*A, mode, y, x, xold, y, c1, c2, s);

@@ -335,11 +335,20 @@ class PSparseMatrix:
     """Device CSR of one part: own rows, columns local to ``plan`` (own, then ghosts)."""
 
     def __init__(self, ctx: Context, M: HCSR, plan: HostPlan | None = None,
-                 dplan: DevicePlan | None = None, row_perm=None, col_perm=None, tag: int = 0):
+                 dplan: DevicePlan | None = None, row_perm=None, col_perm=None, tag: int = 0,
+                 block_size: int = 1):
         """``row_perm`` / ``col_perm`` (pamg_mat_upload_perm): device row i is row
         ``row_perm[i]`` of M, device own column k is own column ``col_perm[k]`` (None: the
         identity); rows keep their storage order, so row sums keep their bits. ``tag``: the
-        column plan's identity (DevicePlan)."""
+        column plan's identity (DevicePlan). ``block_size`` > 1 (pamg_mat_upload_blocked): M is a
+        square node-major operator of that many unknowns per node; where every node's rows store the
+        same whole blocks and no row has a ghost column it takes the block-row layout
+        (``self.blocked``; same bits), otherwise the layouts of a plain upload. Not with a
+        permutation: renumber the nodes before setup."""
+        block_size = int(block_size)
+        if block_size > 1 and (row_perm is not None or col_perm is not None):
+            raise ValueError("PSparseMatrix: block_size > 1 cannot be combined with row_perm / col_perm "
+                             "(the block-row layout has no permuted variant: renumber the nodes before setup)")
         self.ctx = ctx
         if plan is not None and dplan is None and plan.nbrs:
             dplan = DevicePlan(ctx, plan, tag)
@@ -351,7 +360,10 @@ class PSparseMatrix:
             col, ncols = M.col, M.ncols
         col = np.ascontiguousarray(col, np.int32)
         h = C.c_void_p()
-        if row_perm is None and col_perm is None:
+        if block_size != 1:
+            call("pamg_mat_upload_blocked", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
+                 ptr(M.val), 0, dplan.handle if dplan is not None else None, block_size, C.byref(h))
+        elif row_perm is None and col_perm is None:
             call("pamg_mat_upload", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
                  ptr(M.val), 0, dplan.handle if dplan is not None else None, C.byref(h))
         else:
@@ -369,6 +381,11 @@ class PSparseMatrix:
         call("pamg_mat_stream_bytes", h, C.byref(sb))
         self.stream_bytes = sb.value  # matrix bytes one row operation reads (uploaded layout)
         self.block_size = 1
+        self.blocked = False  # the rows run in the block-row layout (pamg_mat_layout bit 15)
+        if block_size != 1:
+            lay = (C.c_int * 10)()
+            call("pamg_mat_layout", h, 0, lay)
+            self.blocked = bool(lay[9] & 32768)
 
     def set_block_diag(self, bs: int = 1, blocks=None, inv=None):
         """Attach the point blocks of the own rows and their inverses (``hcsr.block_diag``'s arrays;

@@ -48,8 +48,23 @@ class _LevelOps:
 
 class AMGSolver:
     def __init__(self, ctx: Context, H: HostHierarchy, part: int = 0, graph: bool | None = None,
-                 reorder: str = "auto"):
-        """``reorder`` (one part only): a locality permutation of every level but the coarsest
+                 reorder: str = "auto", block_layout=None):
+        """``block_layout``: None, a block size (level 0) or a ``{level: block size}`` dict — those
+        levels' operators are uploaded through pamg_mat_upload_blocked and, where they qualify (every
+        node's rows store the same whole blocks, one part without ghost columns), run in the
+        block-row layout: every result keeps its bits, and a point-block sweep (``set_block_size`` with
+        the same size, then a block smoother) is one pass over the matrix instead of two. Such a
+        level must stay unpermuted (ValueError otherwise: build with ``reorder="off"``, and renumber
+        the nodes before setup). Which to take ("Block-row layout"; one MI355X, 80^3 nodes of
+        three unknowns, PCG to 1e-8 with block Chebyshev V(2,2), ``lmax="estimate"``): take it for
+        vector-valued operators whose values do not repeat (finite elements, variable coefficients),
+        most of all where the numbering is not a grid's — 10.8 ms against 14.9 on a randomly
+        renumbered variable-coefficient operator, 7.70 against 7.87 in grid order, the iteration
+        counts equal. Do not take it for a constant-coefficient grid operator like elastic3d: its
+        four distinct values fit the dictionary tiles, which stream a seventh of the bytes (18.3 ms
+        against 37.8 with the block-row layout).
+
+        ``reorder`` (one part only): a locality permutation of every level but the coarsest
         inside the device layout (pamg_locality_order / pamg_mat_upload_perm): "auto" takes
         reverse Cuthill-McKee on the levels whose numbering is scattered (FE meshes, random
         renumberings and the levels aggregated from them), "on" on every level, "off" never.
@@ -91,12 +106,25 @@ class AMGSolver:
                 order, before, after = locality_order(H.levels[l][part].A, mode)
                 self.perm[l] = order
                 self.span[l] = (round(before, 1), round(after, 1))
+        if block_layout is None:
+            block_layout = {}
+        elif not isinstance(block_layout, dict):
+            block_layout = {0: block_layout}
+        self.block_layout = {range(H.nlevels)[int(l)]: int(bs) for l, bs in block_layout.items() if int(bs) != 1}
+        for l, bs in self.block_layout.items():
+            if bs < 1 or bs > 4:
+                raise ValueError(f"block_layout: block size {bs} of level {l} outside 1..4")
+            if self.perm[l] is not None:
+                raise ValueError(f"block_layout: level {l} is uploaded with a locality permutation, which the "
+                                 "block-row layout does not take (build the solver with reorder='off' and "
+                                 "renumber the nodes before setup)")
         for l in range(H.nlevels):
             lp = H.levels[l][part]
             pl = self.perm[l]
             pn = self.perm[l + 1] if l + 1 < H.nlevels else None
             # plan tags (pamg_plan_set_tag): level and operator, the same on every part
-            self.A_dev.append(PSparseMatrix(ctx, lp.A, lp.planA, row_perm=pl, col_perm=pl, tag=plan_tag(l, "A")))
+            self.A_dev.append(PSparseMatrix(ctx, lp.A, lp.planA, row_perm=pl, col_perm=pl, tag=plan_tag(l, "A"),
+                                            block_size=self.block_layout.get(l, 1)))
             self.omega.append(lp.omega)
             if l < H.nlevels - 1:
                 self.P.append(PSparseMatrix(ctx, lp.P, None if l + 1 >= rep else lp.planP,
@@ -238,7 +266,8 @@ class AMGSolver:
         smoother of the same kind on the others. There "gershgorin" means ``rho_b[l]`` (so block
         Jacobi's default weight is 4 / (3 rho_b)), "estimate" the block estimate capped by it, and
         a sequence is taken as given. Each block sweep is the layout's residual pass plus one vector
-        pass (+17 % on a level-0 sweep of elastic3d 80^3). Which to take ("Point-block
+        pass (+17 % on a level-0 sweep of elastic3d 80^3), or a single fused pass on a level in the
+        block-row layout (``AMGSolver(..., block_layout=bs)``). Which to take ("Point-block
         smoothers"; one MI355X, elastic3d 80^3, PCG to 1e-8, ``lmax="estimate"``): block Jacobi V(1,1)
         18.7 ms / 36 iterations against 23.8 / 47 for Jacobi, block Chebyshev V(2,2) 18.1 / 26 against
         19.9 / 30 — the best solve measured; at V(3,3) the block form loses (20.1 / 23 against
