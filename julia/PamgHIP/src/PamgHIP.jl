@@ -436,6 +436,13 @@ function ell_window(A::DeviceMatrix)
     (ell_xwin = out[1] != 0, xwin_groups = Int(out[2]), gather_groups = Int(out[3]), max_window = Int(out[4]),
      noncontig_groups = Int(out[5]), max_pairs = Int(out[6]), max_chunks = Int(out[7]), groups = Int(out[8]))
 end
+"The row classes of a windowed sliced-ELL matrix (`ell_xwin` 1): whether its slices store their distinct rows once, and the census."
+function ell_classes(A::DeviceMatrix)
+    out = zeros(Int64, 8)
+    check(ccall((:pamg_mat_ell_classes, libpamg), Cint, (Ptr{Cvoid}, Ptr{Int64}), A.h, out))
+    (ell_class = out[1] != 0, slices = out[2], classes = out[3], classes_max = out[4], record_bytes = out[5],
+     id_bytes = out[6], replaced_bytes = out[7])
+end
 Base.size(A::DeviceMatrix) = (A.nrows, A.ncols_local)
 
 "mul!(y, A, x): ghost exchange of x (RCCL, overlapped with the interior rows), then y = A x."

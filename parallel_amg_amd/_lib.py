@@ -85,6 +85,7 @@ SIGNATURES = {
     "pamg_mat_stream_bytes": [vp, pi64],
     "pamg_mat_layout": [vp, i32, C.POINTER(C.c_int)],
     "pamg_mat_ell_window": [vp, C.POINTER(C.c_int)],
+    "pamg_mat_ell_classes": [vp, pi64],
     "pamg_mat_set_block_diag": [vp, vp, i32, vp, vp],
     "pamg_mat_block_size": [vp, C.POINTER(C.c_int)],
     "pamg_spmv": [vp, vp, vp, vp],
@@ -221,7 +222,14 @@ def layout_of(M, part_set: int = 0) -> dict:
     win = (C.c_int * 16)()
     if part_set == 0:
         call("pamg_mat_ell_window", M.handle, win)
-    return {"ell_xwin": bool(win[0]), "ell_xwin_groups": int(win[1]), "ell_gather_groups": int(win[2]),
+    cls = (C.c_int64 * 8)()
+    if part_set == 0:
+        call("pamg_mat_ell_classes", M.handle, cls)
+    return {"ell_class": bool(cls[0]),
+            "ell_class_census": {"slices": int(cls[1]), "classes_mean": round(cls[2] / max(cls[1], 1), 2),
+                                 "classes_max": int(cls[3]), "record_bytes": int(cls[4]), "id_bytes": int(cls[5]),
+                                 "replaced_bytes": int(cls[6])},
+            "ell_xwin": bool(win[0]), "ell_xwin_groups": int(win[1]), "ell_gather_groups": int(win[2]),
             "ell_xwin_max_window": int(win[3]), "ell_xwin_noncontig_groups": int(win[4]),
             "ell_xwin_max_pairs": int(win[5]), "ell_xwin_max_chunks": int(win[6]),
             "ell_xwin_census": {"groups": int(win[7]), "full_groups": int(win[13]), "window_mean": int(win[8]),

@@ -1823,8 +1823,10 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ell(int nrows, const int* __
 // 4q .. 4q+3. WIN: the pair byte gives the value and the wave's lof word from LDS, x is read from
 // the staged window at lof + lane (consecutive lanes, consecutive slots); a padded entry reads slot
 // `lane`. Otherwise the pair's offset from LDS and x gathered at row + offset. The same products and
-// sums as k_rows_ell, in the same order.
-template <bool WIN>
+// sums as k_rows_ell, in the same order. FULL: every row of the wave's slice holds these four entries
+// (the class form knows the slice's shortest row), so nothing is selected away: three compares and
+// nine selects fewer per lane and dword, the same sums.
+template <bool WIN, bool FULL = false>
 __device__ __forceinline__ void ellw_dword(uint32_t cq, int q, int L, int lane, int row,
                                            const double* __restrict__ lv, const uint16_t* __restrict__ lof,
                                            const double* __restrict__ lx, const int* __restrict__ lo,
@@ -1840,12 +1842,12 @@ __device__ __forceinline__ void ellw_dword(uint32_t cq, int q, int L, int lane, 
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if constexpr (WIN) xv[e] = lx[4 * q + e < L ? of[e] : lane];
-        else xv[e] = x[4 * q + e < L ? row + of[e] : row];
+        if constexpr (WIN) xv[e] = lx[FULL || 4 * q + e < L ? of[e] : lane];
+        else xv[e] = x[FULL || 4 * q + e < L ? row + of[e] : row];
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const bool ok = 4 * q + e < L;
+        const bool ok = FULL || 4 * q + e < L;
         const double p = vv[e] * xv[e];
         const double t = s + p;
         s = ok ? t : s;
@@ -1853,12 +1855,14 @@ __device__ __forceinline__ void ellw_dword(uint32_t cq, int q, int L, int lane, 
 }
 
 // the index dwords q0 .. q0 + kEllwPre - 1 of a lane's row in one batch of loads (past the slice's
-// last dword: that dword again; a slice without dwords: the stream's first word)
+// last dword: that dword again; a slice without dwords: the stream's first word). `first` is the
+// lane's dword 0 and `stride` the distance to its next: the lane and kEllW in the per-row stream, the
+// row's class and the slice's classes in the class records (EllSet::cls)
 constexpr int kEllwPre = 12;
 __device__ __forceinline__ void ellw_load(uint32_t (&cq)[kEllwPre], const uint32_t* __restrict__ cw, int first, int nq,
-                                          int q0) {
+                                          int q0, int stride) {
 #pragma unroll
-    for (int e = 0; e < kEllwPre; ++e) cq[e] = cw[nq > 0 ? first + min(q0 + e, nq - 1) * kEllW : 0];
+    for (int e = 0; e < kEllwPre; ++e) cq[e] = cw[nq > 0 ? first + min(q0 + e, nq - 1) * stride : 0];
 }
 
 // k_rows_ellw: the windowed sliced ELL (pamg::EllSet::win; the 512^3 level-1 operator). As
@@ -1874,9 +1878,16 @@ __device__ __forceinline__ void ellw_load(uint32_t (&cq)[kEllwPre], const uint32
 // with offset 0, as k_rows_ell finds it; 255: none), its index dword loaded beside the others: no
 // per-entry test in the walk. The window loads read up to one double past the last column (x vectors
 // carry 8 trailing doubles).
-template <int OP>
+// CLS (EllSet::cls): cw holds each slice's distinct rows once, class-interleaved, and cid each row's
+// class: a lane's index dwords are its class's (smeta .y = maxlen | minlen << 8 | classes << 16; the
+// class byte is loaded beside the slice's metadata, so the index loads wait for no more than before).
+// The lanes of a class read the same words: the same dwords in the same registers, from 1-2 lines per
+// wave-load instead of 2, and every sum as without. The dwords below minlen / 4 hold four entries in
+// every row of the slice and are walked without the padding selects (ellw_dword's FULL).
+template <int OP, bool CLS>
 __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* __restrict__ gslices,
                                                          const int2* __restrict__ smeta, const uint32_t* __restrict__ cw,
+                                                         const uint8_t* __restrict__ cid,
                                                          const uint8_t* __restrict__ len, const uint8_t* __restrict__ dpos,
                                                          const int4* __restrict__ gmeta, const int* __restrict__ otab,
                                                          const double* __restrict__ vtab, const int4* __restrict__ wmeta, const int2* __restrict__ chunks,
@@ -1909,8 +1920,13 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
     const int ic = in ? i : 0;
     const int L = in ? (int)len[ic] : 0;
     const int2 sm = smeta[slice >= 0 ? slice : 0];
-    const int nq = slice >= 0 ? (sm.y + 3) >> 2 : 0;
-    const uint32_t* __restrict__ cp = cw + sm.x + lane;
+    const int nq = slice >= 0 ? ((CLS ? sm.y & 0xff : sm.y) + 3) >> 2 : 0;
+    // the dwords every row of the slice fills (wave-uniform, as nq)
+    const int nfull = CLS && slice >= 0 ? __builtin_amdgcn_readfirstlane(((sm.y >> 8) & 0xff) >> 2) : 0;
+    // the lane's first index dword and the distance to its next
+    const int stride = CLS ? sm.y >> 16 : kEllW;
+    const int first = sm.x + (CLS ? (in ? (int)cid[ic] : 0) : lane);
+    const uint32_t* __restrict__ cp = cw + first;
     double pb = 0.0, px = 0.0, py = 0.0, pxo = 0.0;
     if constexpr (OP == OP_RESID || kDiagOp<OP>) pb = b[ic];
     if constexpr (kDiagOp<OP>) px = x[ic];
@@ -1920,12 +1936,12 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
     int dk = 255;
     if constexpr (kDiagOp<OP>) {
         dk = in ? (int)dpos[ic] : 255;
-        dkw = cw[dk != 255 ? sm.x + lane + (dk >> 2) * kEllW : 0];
+        dkw = cw[dk != 255 ? first + (dk >> 2) * stride : 0];
     }
     double s = 0.0;
     if (windowed) {
         uint32_t cq[kEllwPre];
-        ellw_load(cq, cw, sm.x + lane, nq, 0);
+        ellw_load(cq, cw, first, nq, 0, stride);
         for (int k = 0; w + 4 * k < wm.y; ++k) {
             const int col = __builtin_amdgcn_readlane(cmv.x, k), sc = __builtin_amdgcn_readlane(cmv.y, k);
             if (lane < (sc >> 16))
@@ -1938,10 +1954,12 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
         if (tid + 256 < 2 * np) reinterpret_cast<uint32_t*>(lof)[tid + 256] = lb;
         __syncthreads();
         for (int q0 = 0; q0 < nq; q0 += kEllwPre) {
-            if (q0 > 0) ellw_load(cq, cw, sm.x + lane, nq, q0);
+            if (q0 > 0) ellw_load(cq, cw, first, nq, q0, stride);
 #pragma unroll
             for (int e = 0; e < kEllwPre; ++e)
-                if (q0 + e < nq)  // (wave-uniform)
+                if (CLS && q0 + e < nfull)
+                    ellw_dword<true, true>(cq[e], q0 + e, L, lane, ic, lv, lof + w * np, lx, nullptr, x, s);
+                else if (q0 + e < nq)  // (wave-uniform)
                     ellw_dword<true>(cq[e], q0 + e, L, lane, ic, lv, lof + w * np, lx, nullptr, x, s);
         }
     } else {
@@ -1955,7 +1973,7 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
         uint32_t c4 = nq > 0 ? cp[0] : 0u;
         for (int q = 0; q < nq; ++q) {
             const uint32_t cq = c4;
-            if (q + 1 < nq) c4 = cp[(q + 1) * kEllW];  // the next dword in flight while this one is used
+            if (q + 1 < nq) c4 = cp[(q + 1) * stride];  // the next dword in flight while this one is used
             ellw_dword<false>(cq, q, L, lane, ic, lv, nullptr, nullptr, lo, x, s);
         }
     }
@@ -3034,10 +3052,14 @@ void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const
         if (E.win) {
             const int win = std::max(E.max_window, 128);
             const size_t lds = sizeof(double) * (size_t)(win + 256) + sizeof(uint16_t) * 4 * 256;
-            k_rows_ellw<OP><<<grid, kEllGroup, lds, s>>>(
-                (int)A.nrows, E.d_gslices, E.d_smeta, E.d_ci, E.d_len, E.d_dpos, E.d_gmeta, E.d_otab, E.d_vtab, E.d_wmeta,
-                E.d_chunks, E.d_lof, win, (reinterpret_cast<uintptr_t>(x) & 15) != 0 ? 1 : 0, (int)E.ngroups, x, b, y,
-                omega, ch.c1, ch.xold);
+            auto gow = [&](auto kern) {
+                kern<<<grid, kEllGroup, lds, s>>>((int)A.nrows, E.d_gslices, E.d_smeta, E.d_ci, E.d_cid, E.d_len, E.d_dpos,
+                                                  E.d_gmeta, E.d_otab, E.d_vtab, E.d_wmeta, E.d_chunks, E.d_lof, win,
+                                                  (reinterpret_cast<uintptr_t>(x) & 15) != 0 ? 1 : 0, (int)E.ngroups, x, b,
+                                                  y, omega, ch.c1, ch.xold);
+            };
+            if (E.cls) gow(k_rows_ellw<OP, true>);
+            else gow(k_rows_ellw<OP, false>);
         } else if (E.d_anc) {
             if (E.paired) go(k_rows_ell<OP, true, true>);
             else go(k_rows_ell<OP, true, false>);

@@ -1112,6 +1112,73 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
             std::copy(glof[g].begin(), glof[g].end(), lof.begin() + wmeta[g].z);
         }
     });
+    // Row classes (Options::ell_xwin 1 — 2 keeps the per-row stream —, EllSet::cls): the rows of a slice in classes of equal length,
+    // diagonal position and pair bytes (the stream's padding bytes are 0, so equal dwords and equal
+    // lengths are equal rows), numbered by first appearance; the slice then stores one padded row per
+    // class, class-interleaved, and a class byte per row. Taken where that is at most half of the
+    // per-row stream's bytes (the 512^3 A1: ~6 classes per slice of 64 rows).
+    std::vector<int2> smeta_c;
+    std::vector<uint32_t> ccw;
+    std::vector<uint8_t> cid;
+    if (pamg::options().ell_xwin == 1) {
+        std::vector<int> snc(ns, 0), smin(ns, 0);
+        cid.assign(n + kVecPad, 0);
+        par_for(ns, [&](int64_t a, int64_t b) {
+            int rep[kEllW];
+            for (int64_t q = a; q < b; ++q) {
+                const int nq = (smeta[q].y + 3) / 4;
+                const int64_t r0 = q * kEllW, s0 = smeta[q].x;
+                const int rows = (int)std::min<int64_t>(n - r0, kEllW);
+                int nc = 0;
+                for (int l = 0; l < rows; ++l) {
+                    int c = 0;
+                    for (; c < nc; ++c) {
+                        const int m = rep[c];
+                        bool same = len[r0 + l] == len[r0 + m] && dpos[r0 + l] == dpos[r0 + m];
+                        for (int k = 0; k < nq && same; ++k) same = cw[s0 + (int64_t)k * kEllW + l] == cw[s0 + (int64_t)k * kEllW + m];
+                        if (same) break;
+                    }
+                    if (c == nc) rep[nc++] = l;
+                    cid[r0 + l] = (uint8_t)c;
+                }
+                snc[q] = nc;
+                // the slice's shortest row (a partial slice: 0 — its idle lanes hold no row)
+                int lmin = rows == kEllW ? 255 : 0;
+                for (int l = 0; l < rows; ++l) lmin = std::min<int>(lmin, len[r0 + l]);
+                smin[q] = lmin;
+            }
+        });
+        smeta_c.resize(ns);
+        int64_t cwords = 0;
+        for (int64_t q = 0; q < ns; ++q) {
+            smeta_c[q] = make_int2((int)cwords, smeta[q].y | smin[q] << 8 | snc[q] << 16);
+            cwords += (int64_t)snc[q] * ((smeta[q].y + 3) / 4);
+            E.cls_total += snc[q];
+            E.cls_max = std::max(E.cls_max, snc[q]);
+        }
+        if (2 * (4 * cwords + n) <= 4 * words) {
+            E.cls = true;
+            E.cls_words = cwords;
+            ccw.assign(cwords + 1, 0u);
+            par_for(ns, [&](int64_t a, int64_t b) {
+                for (int64_t q = a; q < b; ++q) {
+                    const int nq = (smeta[q].y + 3) / 4, nc = snc[q];
+                    const int64_t r0 = q * kEllW, s0 = smeta[q].x;
+                    const int rows = (int)std::min<int64_t>(n - r0, kEllW);
+                    for (int l = 0; l < rows; ++l)  // (every row of a class writes the same dwords)
+                        for (int k = 0; k < nq; ++k)
+                            ccw[smeta_c[q].x + (int64_t)k * nc + cid[r0 + l]] = cw[s0 + (int64_t)k * kEllW + l];
+                }
+            });
+            std::vector<uint32_t>().swap(cw);
+        } else {
+            E.cls_total = 0;
+            E.cls_max = 0;
+        }
+    }
+    const std::vector<int2>& sm_up = E.cls ? smeta_c : smeta;
+    const std::vector<uint32_t>& cw_up = E.cls ? ccw : cw;
+    const int64_t up_words = E.cls ? E.cls_words : words;
     pamg_ctx* ctx = A->ctx;
     E.nslices = ns;
     E.ngroups = ng;
@@ -1123,7 +1190,11 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     E.nchunks = cn;
     E.lof_n = ln;
     CHECK(dalloc(&E.d_smeta, ns));
-    CHECK(dalloc(&E.d_ci, words + 1));
+    CHECK(dalloc(&E.d_ci, up_words + 1));
+    if (E.cls) {
+        CHECK(dalloc(&E.d_cid, n + kVecPad));
+        CHECK(h2d(ctx, E.d_cid, cid.data(), cid.size()));
+    }
     CHECK(dalloc(&E.d_len, n + kVecPad));
     CHECK(dalloc(&E.d_gmeta, ng));
     CHECK(dalloc(&E.d_otab, on + 1));
@@ -1134,8 +1205,8 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     CHECK(dalloc(&E.d_lof, ln + 2));
     CHECK(dalloc(&E.d_dpos, n + kVecPad));
     CHECK(h2d(ctx, E.d_dpos, dpos.data(), dpos.size()));
-    CHECK(h2d(ctx, E.d_smeta, smeta.data(), sizeof(int2) * ns));
-    CHECK(h2d(ctx, E.d_ci, cw.data(), sizeof(uint32_t) * (words + 1)));
+    CHECK(h2d(ctx, E.d_smeta, sm_up.data(), sizeof(int2) * ns));
+    CHECK(h2d(ctx, E.d_ci, cw_up.data(), sizeof(uint32_t) * (up_words + 1)));
     CHECK(h2d(ctx, E.d_len, len.data(), len.size()));
     CHECK(h2d(ctx, E.d_gmeta, gmeta.data(), sizeof(int4) * ng));
     CHECK(h2d(ctx, E.d_otab, otab.data(), sizeof(int) * (on + 1)));
@@ -1388,7 +1459,9 @@ int ell_try(Upload& u) {
 int64_t ell_bytes(const pamg_mat* A) {
     if (!A->interior.ell) return 0;
     const int64_t nrows = A->nrows;
-    return (A->ell.paired ? 4 : 8) * A->ell.words + nrows + 8 * A->ell.nslices + 16 * A->ell.ngroups + 4 * A->ell.otab_n +
+    // (row classes: the class records and a class byte per row in place of the per-row stream)
+    const int64_t index = A->ell.cls ? 4 * A->ell.cls_words + nrows : (A->ell.paired ? 4 : 8) * A->ell.words;
+    return index + nrows + 8 * A->ell.nslices + 16 * A->ell.ngroups + 4 * A->ell.otab_n +
            8 * A->ell.vtab_n + (A->ell.d_anc ? 4 * nrows : 0) +
            (A->ell.win ? 32 * A->ell.ngroups + 8 * A->ell.nchunks + 2 * A->ell.lof_n + nrows : 0);
 }
@@ -1419,7 +1492,22 @@ void ell_window(const pamg_mat* A, int out[16]) {
     out[14] = out[15] = 0;
 }
 
+// the row classes of a windowed operator (pamg_mat_ell_classes)
+void ell_classes(const pamg_mat* A, int64_t out[8]) {
+    const pamg::EllSet& E = A->ell;
+    const bool c = A->interior.ell && E.cls;
+    out[0] = c ? 1 : 0;
+    out[1] = c ? E.nslices : 0;
+    out[2] = c ? E.cls_total : 0;
+    out[3] = c ? E.cls_max : 0;
+    out[4] = c ? 4 * E.cls_words : 0;
+    out[5] = c ? A->nrows : 0;
+    out[6] = c ? 4 * E.words : 0;
+    out[7] = 0;
+}
+
 void ell_free(pamg::EllSet& E) {
+    dfree(E.d_cid);
     dfree(E.d_gorder);
     dfree(E.d_smeta);
     dfree(E.d_ci);
@@ -2962,6 +3050,12 @@ int pamg_mat_layout(const pamg_mat* A, int set, int out[10]) {
 int pamg_mat_ell_window(const pamg_mat* A, int out[16]) {
     if (!A || !out) return fail(PAMG_E_ARG, "mat_ell_window: bad args");
     ell_window(A, out);
+    return PAMG_OK;
+}
+
+int pamg_mat_ell_classes(const pamg_mat* A, int64_t out[8]) {
+    if (!A || !out) return fail(PAMG_E_ARG, "mat_ell_classes: bad args");
+    ell_classes(A, out);
     return PAMG_OK;
 }
 

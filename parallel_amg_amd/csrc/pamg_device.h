@@ -161,7 +161,10 @@ struct Options {
     int ell_xwin = 1;          // 1: windowed ELL for whole square one-part operators with pair tables (EllSet::win):
                                //    groups of 4 coupled slices whose x neighbourhood is staged in LDS. Taken where
                                //    >= kEllWinMinShare percent of the groups are windowed and their nonzeros per
-                               //    window entry are >= kEllWinMinRatio100 / 100 (below: the thresholds)
+                               //    window entry are >= kEllWinMinRatio100 / 100 (below: the thresholds). With 1
+                               //    a windowed operator also stores each slice's distinct rows once, and a class
+                               //    byte per row, where that at least halves its index bytes (EllSet::cls);
+                               //    2: windowed, always the per-row index stream
     int ell_xwin_max = 7168;   // window capacity in doubles (<= kEllWinCap, the kernel's: 56 KB of its 60 KB of LDS)
     int pnc_compact = 1;       // 1: 16-bit combination ids instead of 64-bit records where <= kPncCombMax fit
     int pnc = 1;               // != 0: neighbour-coded prolongations over a grid registered on the context (PncSet);
@@ -252,6 +255,19 @@ struct EllSet {
     int max_window = 0, max_pairs = 0, max_chunks = 0;  // over the windowed groups (max_pairs: all groups)
     // census of the upload (pamg_mat_ell_window): windows, runs and pairs per windowed group, 4-slice groups
     int mean_window = 0, p95_window = 0, mean_runs = 0, max_runs = 0, mean_pairs = 0, full_groups = 0;
+    // row classes (Options::ell_xwin 1; windowed operators): two rows of a slice are one class where their
+    // length, diagonal position and pair bytes are equal. d_ci then holds every slice's classes once, padded
+    // to the slice's dwords and class-interleaved — dword q of class c at start + q * nc + c, d_smeta .y =
+    // maxlen | minlen << 8 | nc << 16 (minlen: the slice's shortest row, 0 for a partial slice: the dwords
+    // below minlen / 4 hold no padding, and the kernel walks them without its selects) — and d_cid each
+    // row's class within its slice. Taken where the class records and the id bytes are at most half of
+    // the per-row stream (below that the kernel's loads are the same in number, their lines fewer);
+    // `words` stays the per-row stream's size, for the census.
+    bool cls = false;
+    uint8_t* d_cid = nullptr;
+    int64_t cls_words = 0;
+    int cls_max = 0;             // most classes of a slice
+    int64_t cls_total = 0;       // classes over all slices
 };
 
 // Neighbour-coded prolongation (Options::pnc; round 5, the 512^3 P0): a prolongation (more rows than
