@@ -28,6 +28,7 @@ def bits(a):
     (3, "poisson2d", 60, 200, 0),
     (4, "poisson3d", 24, 60, 0),          # interior parts with two neighbours
     (2, "poisson2d", 20, 1000, 0),        # one level: the distributed coarsest solve
+    (3, "poisson2d", 36, 2000, 0),        # one level of 1,296 rows: row offsets != 0, a second 1,024-column chunk
     (2, "poisson2d", 256, 1000, 0),       # BASELINE.json configs[0] at its size (golden test below)
     (8, "poisson3d", 64, 1000, 0),        # BASELINE.json configs[2]'s part count; z-slabs: the
     (8, "aniso3d", 64, 1000, 32768),      # blocked level-0 passes run on every part (tb_part)
@@ -41,6 +42,8 @@ def test_local_world_vcycle_bit_exact(built, nparts, kind, n, max_coarse, agglom
             A, offs, xs = pa.generate_problem(be, kind, n)
             H = pa.build_hierarchy(be, A, offs, pa.SAParams(max_coarse=max_coarse, agglomerate=agglomerate),
                                    device=W.ctxs[0])
+            if kind == "poisson2d" and n * n <= max_coarse:
+                assert H.nlevels == 1   # (the dense solve of the parts' own rows is the whole cycle)
             S = [AMGSolver(W.ctxs[p], H, part=p) for p in range(nparts)]
             assert all(not s.graph_state()["enabled"] for s in S)   # synchronous transport: eager
             A0 = [s.A[0] for s in S]

@@ -123,6 +123,7 @@ def _worker(rank, world, port, kind, n, max_coarse, agglomerate, ncycles, poison
     (3, "poisson2d", 60, 200, 0, 1),
     (3, "aniso3d", 16, 30, 600, 1),        # agglomerated from level 2 on
     (2, "poisson2d", 20, 1000, 0, 0),      # one level: the distributed coarsest solve
+    (3, "poisson2d", 36, 2000, 0, 1),      # one level of 1,296 rows: row offsets != 0, a second 1,024-column chunk
     (4, "poisson3d", 24, 60, 0, 1),        # four parts, interior parts with two neighbours
     # eight parts (BASELINE.json configs[2]'s part count) at a size the oracle sets up in
     # seconds: decoupled on every level and agglomerated (SPEC §S7)
@@ -148,6 +149,8 @@ def test_multipart_vcycle_bit_exact(world, kind, n, max_coarse, agglomerate, poi
     bo = O.spmv(Ao, O.xstar(Ao.nrows))
     Ho = O.setup(Ao, nparts=world, max_coarse=max_coarse, agglomerate=agglomerate)
     xo, ho = Ho.solve(bo, ncycles, res_hist=True)
+    if kind == "poisson2d" and n * n <= max_coarse:
+        assert Ho.nlevels == 1   # (the dense solve of the ranks' own rows is the whole cycle)
     b = np.concatenate([res[r][2] for r in range(world)])
     x = np.concatenate([res[r][3] for r in range(world)])
     bits = lambda a: np.asarray(a, np.float64).view(np.int64)

@@ -333,19 +333,25 @@ def test_pcg_matches_oracle(ctx, kind, n, max_coarse):
     assert np.linalg.norm(xg - xs[0]) <= 1e-8 * np.linalg.norm(xs[0])
 
 
-def test_pcg_equals_primitive_sequence(ctx):
+@pytest.mark.parametrize("kind,n,max_coarse,maxit", [("poisson3d", 20, 100, 40), ("poisson2d", 520, 1000, 3)])
+def test_pcg_equals_primitive_sequence(ctx, kind, n, max_coarse, maxit):
     """pamg_pcg (fused x / r update + r.r in one kernel) gives the bits of the same CG written
-    with the separate C-ABI primitives (mul, dot, axpby, V-cycle from zero)."""
+    with the separate C-ABI primitives (mul, dot, axpby, V-cycle from zero). poisson2d 520 has
+    270,400 rows: the 1,024-block grid of the reductions wraps (three iterations, all compared).
+    The first history entry is the restated dot of test_gpu_reductions.py: with x = 0, r is b."""
     from parallel_amg_amd.partitioned import copy
+    from test_gpu_reductions import restated_dot
     be = pa.SequentialBackend(1)
-    A, offs, xs = pa.generate_problem(be, "poisson3d", 20)
-    H = pa.build_hierarchy(be, A, offs, pa.SAParams(max_coarse=100))
+    A, offs, xs = pa.generate_problem(be, kind, n)
+    H = pa.build_hierarchy(be, A, offs, pa.SAParams(max_coarse=max_coarse))
     S = AMGSolver(ctx, H)
     A0 = S.A[0]
     b = PVector(ctx, A0.nrows)
     mul(b, A0, PVector(ctx, A0.nrows, 0, xs[0]))
     x1 = S.new_vector()
-    k1, h1 = S.pcg(x1, b, 1e-9, 40)
+    k1, h1 = S.pcg(x1, b, 1e-9, maxit)
+    bh = b.own_values()
+    assert np.array_equal(bits(h1[0]), bits(np.sqrt(np.float64(restated_dot(bh, bh)))))
 
     x = S.new_vector()
     r, z, p, q = S.new_vector(), S.new_vector(), S.new_vector(), S.new_vector()
@@ -357,7 +363,7 @@ def test_pcg_equals_primitive_sequence(ctx):
     copy(p, z)
     rz = dot(r, z)
     k = 0
-    while k < 40:
+    while k < maxit:
         k += 1
         mul(q, A0, p)
         alpha = rz / dot(p, q)
