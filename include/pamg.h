@@ -243,6 +243,12 @@ int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
  * and 95th-percentile window, out[10] / out[11] the mean and largest number of column runs, out[12]
  * the mean pair table, out[13] the groups of 4 slices; out[14], out[15] 0. */
 int pamg_mat_ell_window(const pamg_mat* A, int out[16]);
+/* The group pairs of a windowed sliced-ELL matrix (ell_xwin 1 | 2: two windowed groups whose windows
+ * overlap run in one workgroup on their union window): out[0] the pairs, out[1] the windowed groups
+ * left single, out[2] / out[3] the mean and 95th-percentile union window (doubles), out[4] the mean of
+ * union / (the two windows together) in percent, out[5] the largest union; out[6], out[7] 0. All 0
+ * where the matrix does not run in the layout. */
+int pamg_mat_ell_span(const pamg_mat* A, int out[8]);
 /* The row classes of a windowed sliced-ELL matrix (ell_xwin 1): out[0] 1 where every slice stores its
  * distinct rows once and a class byte per row (else all 0), out[1] the slices, out[2] the classes over
  * all slices, out[3] the most classes of a slice, out[4] the bytes of the class records, out[5] of the
@@ -440,9 +446,11 @@ int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps
  * rows for restrictions whose rows repeat <= 255 patterns; tried before ELL), "pnc_compact" (0 | 1:
  * neighbour-coded rows as 16-bit ids of <= 1024 (pattern, values) combinations), "ell_pair" (0 | 1:
  * one ELL index byte per nonzero naming an (offset, value) pair where a group has <= 256), "ell_xwin"
- * (0 | 1 | 2: windowed ELL for whole square one-part operators with pair tables — groups of 4 coupled
+ * (0 .. 4: windowed ELL for whole square one-part operators with pair tables — groups of 4 coupled
  * slices, their x neighbourhood staged in LDS; 1 also stores each slice's distinct rows once and a
- * class byte per row where that at least halves the index bytes, 2 never), "ell_xwin_max" (2..7168:
+ * class byte per row where that at least halves the index bytes, 2 never; with 1 and 2 windowed groups
+ * whose windows overlap run two to a workgroup on one union window — pamg_mat_ell_span —, 3 and 4 are
+ * 1 and 2 without that), "ell_xwin_max" (2..7168:
  * window capacity in doubles; a larger group gathers). Read at launch:
  * "sym_zm" (0 | 1: z-marching single sweeps of the symmetric layout), "zm_chunks" (0 = auto |
  * z chunks per column of k_sym_zm), "tb_xfast" (0 | 1: x-fastest tile order of the chain),

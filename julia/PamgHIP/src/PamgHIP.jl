@@ -436,6 +436,13 @@ function ell_window(A::DeviceMatrix)
     (ell_xwin = out[1] != 0, xwin_groups = Int(out[2]), gather_groups = Int(out[3]), max_window = Int(out[4]),
      noncontig_groups = Int(out[5]), max_pairs = Int(out[6]), max_chunks = Int(out[7]), groups = Int(out[8]))
 end
+"The group pairs of a windowed sliced-ELL matrix (`ell_xwin` 1 or 2): pairs, groups left single, and the union windows."
+function ell_span(A::DeviceMatrix)
+    out = zeros(Cint, 8)
+    check(ccall((:pamg_mat_ell_span, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cint}), A.h, out))
+    (pairs = Int(out[1]), singles = Int(out[2]), union_mean = Int(out[3]), union_p95 = Int(out[4]),
+     union_ratio = out[5] / 100, union_max = Int(out[6]))
+end
 "The row classes of a windowed sliced-ELL matrix (`ell_xwin` 1): whether its slices store their distinct rows once, and the census."
 function ell_classes(A::DeviceMatrix)
     out = zeros(Int64, 8)

@@ -85,6 +85,7 @@ SIGNATURES = {
     "pamg_mat_stream_bytes": [vp, pi64],
     "pamg_mat_layout": [vp, i32, C.POINTER(C.c_int)],
     "pamg_mat_ell_window": [vp, C.POINTER(C.c_int)],
+    "pamg_mat_ell_span": [vp, C.POINTER(C.c_int)],
     "pamg_mat_ell_classes": [vp, pi64],
     "pamg_mat_set_block_diag": [vp, vp, i32, vp, vp],
     "pamg_mat_block_size": [vp, C.POINTER(C.c_int)],
@@ -222,8 +223,10 @@ def layout_of(M, part_set: int = 0) -> dict:
     win = (C.c_int * 16)()
     if part_set == 0:
         call("pamg_mat_ell_window", M.handle, win)
+    span = (C.c_int * 8)()
     cls = (C.c_int64 * 8)()
     if part_set == 0:
+        call("pamg_mat_ell_span", M.handle, span)
         call("pamg_mat_ell_classes", M.handle, cls)
     return {"ell_class": bool(cls[0]),
             "ell_class_census": {"slices": int(cls[1]), "classes_mean": round(cls[2] / max(cls[1], 1), 2),
@@ -234,7 +237,11 @@ def layout_of(M, part_set: int = 0) -> dict:
             "ell_xwin_max_pairs": int(win[5]), "ell_xwin_max_chunks": int(win[6]),
             "ell_xwin_census": {"groups": int(win[7]), "full_groups": int(win[13]), "window_mean": int(win[8]),
                                 "window_p95": int(win[9]), "runs_mean": int(win[10]), "runs_max": int(win[11]),
-                                "pairs_mean": int(win[12])},
+                                "pairs_mean": int(win[12]),
+                                # group pairs (ell_xwin 1 | 2; pamg_mat_ell_span)
+                                "span_pairs": int(span[0]), "span_singles": int(span[1]),
+                                "union_mean": int(span[2]), "union_p95": int(span[3]),
+                                "union_ratio": span[4] / 100.0, "union_max": int(span[5])},
             "c24": bool(out[0]), "vd": bool(out[1]), "rl8": bool(out[2]), "cd": int(out[3]),
             "cd_offsets": int(out[4]), "tm": bool(out[5]), "tm_rs": int(out[6]),
             "tile_nnz": int(out[7]), "tiles": int(out[8]), "anchored": bool(out[9] & 1), "per_tile": bool(out[9] & 2),

@@ -1884,36 +1884,58 @@ __device__ __forceinline__ void ellw_load(uint32_t (&cq)[kEllwPre], const uint32
 // The lanes of a class read the same words: the same dwords in the same registers, from 1-2 lines per
 // wave-load instead of 2, and every sum as without. The dwords below minlen / 4 hold four entries in
 // every row of the slice and are walked without the padding selects (ellw_dword's FULL).
-template <int OP, bool CLS>
-__global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* __restrict__ gslices,
+// SPAN 2 (EllSet::npairs, Options::ell_xwin 1 | 2): a workgroup of 8 waves takes pair g's two groups,
+// waves 0-3 the slices of the first and waves 4-7 of the second, from the pair's record (4 int4 of
+// `pairs`, found from blockIdx alone) instead of gmeta / wmeta / gslices. All 8 waves issue the chunk
+// loads of the pair's one union window (lane k of wave w: chunk w + 8k), either half stages its own
+// group's values and lof words — which point into the union window — behind them, and after the one
+// barrier a lane walks its row as in SPAN 1: the same operands, products and sums. Pairs are always
+// windowed (dynamic LDS: [win] doubles, 2 x 256 values, 2 x 4 x 256 lof words); where x is not
+// 16-byte aligned the launcher runs their groups in SPAN 1. SPAN 1 takes the groups g0 + 0 .. ngroups - 1.
+template <int OP, bool CLS, int SPAN = 1>
+__global__ __launch_bounds__(SPAN * kEllGroup) void k_rows_ellw(int nrows, const int4* __restrict__ gslices,
                                                          const int2* __restrict__ smeta, const uint32_t* __restrict__ cw,
                                                          const uint8_t* __restrict__ cid,
                                                          const uint8_t* __restrict__ len, const uint8_t* __restrict__ dpos,
                                                          const int4* __restrict__ gmeta, const int* __restrict__ otab,
                                                          const double* __restrict__ vtab, const int4* __restrict__ wmeta, const int2* __restrict__ chunks,
                                                          const uint16_t* __restrict__ lofs, int win, int gather_all,
+                                                         const int4* __restrict__ pairs, int g0,
                                                          int ngroups, const double* __restrict__ x,
                                                          const double* __restrict__ b, double* __restrict__ y,
                                                          double omega, double c1 = 0.0,
                                                          const double* __restrict__ xold = nullptr) {
     extern __shared__ double ellw_lds[];
     double* lx = ellw_lds;
-    double* lv = ellw_lds + win;
-    uint16_t* lof = reinterpret_cast<uint16_t*>(lv + 256);
     const int per = (ngroups + 7) / 8;
-    const int g = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    if (g >= ngroups) return;  // the whole workgroup, before the barrier
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int4 gm = gmeta[g], wm = wmeta[g], gs = gslices[g];
+    const int gl = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    if (gl >= ngroups) return;  // the whole workgroup, before the barrier
+    const int g = g0 + gl;
+    const int lane = threadIdx.x & 63, tid = threadIdx.x & (kEllGroup - 1);  // (tid: within the thread's group)
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int w = wv & 3, half = wv >> 2;  // the wave within its group; the group of the pair
+    double* lv = ellw_lds + win + 256 * half;
+    uint16_t* lof = reinterpret_cast<uint16_t*>(ellw_lds + win + 256 * SPAN) + 4 * 256 * half;
+    int4 gm, wm, gs;
+    if constexpr (SPAN == 2) {
+        const int4 ra = pairs[4 * g], rb = pairs[4 * g + 1], rt = pairs[4 * g + 2], rw = pairs[4 * g + 3];
+        gs = half ? rb : ra;
+        gm = half ? make_int4(rt.z, rt.w, rt.z, rt.w) : make_int4(rt.x, rt.y, rt.x, rt.y);
+        wm = make_int4(rw.x, rw.y & 0xffff, half ? rw.w : rw.z, rw.y >> 16);
+    } else {
+        gm = gmeta[g];
+        wm = wmeta[g];
+        gs = gslices[g];
+    }
     // what depends on the group alone first: the tables, the lof words and the wave's chunk words (lane k:
-    // chunk w + 4k; <= kEllWinChunks / 4 = 64 a wave) are in flight with the slice's metadata
+    // chunk w + 4k; <= kEllWinChunks / 4 = 64 a wave — a pair: wv + 8k of <= kEllSpanChunks) are in
+    // flight with the slice's metadata
     const int np = gm.y;
-    const bool windowed = wm.y > 0 && !gather_all;
+    const bool windowed = SPAN == 2 || (wm.y > 0 && !gather_all);
     const double vtv = vtab[gm.x + (tid < np ? tid : 0)];
     const uint32_t* __restrict__ l32 = reinterpret_cast<const uint32_t*>(lofs + wm.z);  // (wm.z: a multiple of 4)
     const uint32_t la = l32[windowed && tid < 2 * np ? tid : 0], lb = l32[windowed && tid + 256 < 2 * np ? tid + 256 : 0];
-    const int2 cmv = chunks[wm.x + (w + 4 * lane < wm.y ? w + 4 * lane : 0)];
+    const int2 cmv = chunks[wm.x + (wv + 4 * SPAN * lane < wm.y ? wv + 4 * SPAN * lane : 0)];
     const int slice = w == 0 ? gs.x : w == 1 ? gs.y : w == 2 ? gs.z : gs.w;
     const int i = slice * kEllW + lane;
     const bool in = slice >= 0 && i < nrows;
@@ -1942,7 +1964,7 @@ __global__ __launch_bounds__(kEllGroup) void k_rows_ellw(int nrows, const int4* 
     if (windowed) {
         uint32_t cq[kEllwPre];
         ellw_load(cq, cw, first, nq, 0, stride);
-        for (int k = 0; w + 4 * k < wm.y; ++k) {
+        for (int k = 0; wv + 4 * SPAN * k < wm.y; ++k) {
             const int col = __builtin_amdgcn_readlane(cmv.x, k), sc = __builtin_amdgcn_readlane(cmv.y, k);
             if (lane < (sc >> 16))
                 __builtin_amdgcn_global_load_lds(
@@ -3051,15 +3073,26 @@ void launch_rows_op(const pamg_mat& A, const TileSet& ts, const double* x, const
         };
         if (E.win) {
             const int win = std::max(E.max_window, 128);
-            const size_t lds = sizeof(double) * (size_t)(win + 256) + sizeof(uint16_t) * 4 * 256;
-            auto gow = [&](auto kern) {
-                kern<<<grid, kEllGroup, lds, s>>>((int)A.nrows, E.d_gslices, E.d_smeta, E.d_ci, E.d_cid, E.d_len, E.d_dpos,
-                                                  E.d_gmeta, E.d_otab, E.d_vtab, E.d_wmeta, E.d_chunks, E.d_lof, win,
-                                                  (reinterpret_cast<uintptr_t>(x) & 15) != 0 ? 1 : 0, (int)E.ngroups, x, b,
-                                                  y, omega, ch.c1, ch.xold);
+            // the pairs two groups to a workgroup (x not 16-byte aligned: nothing is staged, every group
+            // alone), then the groups left single; disjoint rows, one stream
+            const int gather_all = (reinterpret_cast<uintptr_t>(x) & 15) != 0 ? 1 : 0;
+            const int npairs = gather_all ? 0 : E.npairs, nrest = (int)E.ngroups - 2 * npairs;
+            auto gow = [&](auto kern, int span, int g0, int n, int wn) {
+                const size_t bytes = sizeof(double) * (size_t)(wn + 256 * span) + sizeof(uint16_t) * 4 * 256 * span;
+                kern<<<(n + 7) / 8 * 8, span * kEllGroup, bytes, s>>>(
+                    (int)A.nrows, E.d_gslices, E.d_smeta, E.d_ci, E.d_cid, E.d_len, E.d_dpos, E.d_gmeta, E.d_otab,
+                    E.d_vtab, E.d_wmeta, E.d_chunks, E.d_lof, wn, gather_all, E.d_pairs, g0, n, x, b, y, omega, ch.c1,
+                    ch.xold);
             };
-            if (E.cls) gow(k_rows_ellw<OP, true>);
-            else gow(k_rows_ellw<OP, false>);
+            if (npairs > 0) {
+                const int wu = std::max(E.max_union, 128);
+                if (E.cls) gow(k_rows_ellw<OP, true, 2>, 2, 0, npairs, wu);
+                else gow(k_rows_ellw<OP, false, 2>, 2, 0, npairs, wu);
+            }
+            if (nrest > 0) {
+                if (E.cls) gow(k_rows_ellw<OP, true>, 1, 2 * npairs, nrest, win);
+                else gow(k_rows_ellw<OP, false>, 1, 2 * npairs, nrest, win);
+            }
         } else if (E.d_anc) {
             if (E.paired) go(k_rows_ell<OP, true, true>);
             else go(k_rows_ell<OP, true, false>);

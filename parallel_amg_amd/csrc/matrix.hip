@@ -22,6 +22,7 @@
 
 #include "pamg_device.h"
 #include "pamg_host.h"
+#include "ell_span.h"
 
 namespace {
 
@@ -925,6 +926,10 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     std::vector<std::vector<uint16_t>> glof(ng);
     std::vector<int> gwin(ng, 0), gruns(ng, 0);
     std::vector<int64_t> gnnz(ng, 0);
+    // (group pairs, below: every windowed group's runs and, per lof word, the first lane that reads it)
+    const bool span2 = pamg::options().ell_xwin <= 2;  // (3, 4: single groups only)
+    std::vector<pamg::EllRuns> gwruns(span2 ? ng : 0);
+    std::vector<std::vector<uint8_t>> glmin(span2 ? ng : 0);
     std::vector<uint32_t> cw(words + 1, 0u);
     std::vector<uint8_t> len(n + kVecPad, 0), dpos(n + kVecPad, (uint8_t)255);
     par_for(ng, [&](int64_t a, int64_t b) {
@@ -1014,6 +1019,10 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
                 for (int c = r[0]; c < r[1]; c += 128)
                     gchunk[g].push_back(make_int2(c, (r[2] + c - r[0]) | (std::min(128, r[1] - c) / 2) << 16));
             glof[g].assign((size_t)4 * np, (uint16_t)64);
+            if (span2) {
+                gwruns[g] = runs;
+                glmin[g].assign((size_t)4 * np, (uint8_t)255);
+            }
             for (int w = 0; w < 4; ++w)
                 for (int p = 0; p < np; ++p) {
                     uint16_t word = 64;
@@ -1022,6 +1031,7 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
                         size_t r = 0;
                         while (r + 1 < runs.size() && runs[r + 1][0] <= c) ++r;
                         word = (uint16_t)(runs[r][2] + c0 - runs[r][0] + 64);
+                        if (span2) glmin[g][(size_t)w * np + p] = (uint8_t)lmin[w * 256 + p];
                     }
                     glof[g][(size_t)w * np + p] = word;
                 }
@@ -1046,6 +1056,7 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
                     gwin[g] = 0;
                     gchunk[g].clear();
                     glof[g].clear();
+                    if (span2) gwruns[g].clear();
                 }
             break;
         }
@@ -1085,12 +1096,85 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
         E.mean_runs = (int)(win_runs / E.win_groups);
         E.mean_pairs = (int)(win_pairs / E.win_groups);
     }
+    // Group pairs (Options::ell_xwin 1 | 2; pamg_device.h, ell_span.h): windowed groups coupled two
+    // and two where their union window pays, the groups renumbered pairs first — pair p = groups 2p,
+    // 2p + 1, then the rest in their order (no pair: nothing moves, the layout is span 1's) —; a pair's
+    // chunks are its union window's, stored with its first group, and both groups' lof words point
+    // into that window.
+    std::vector<int> gunion(ng, 0);  // per renumbered group: its pair's union window (0: single)
+    if (span2) {
+        std::vector<int> sgroup(ns, -1);
+        for (int64_t g = 0; g < ng; ++g)
+            for (int w = 0; w < 4; ++w)
+                if (grp[g][w] >= 0) sgroup[grp[g][w]] = (int)g;
+        const std::vector<std::pair<int, int>> prs =
+            pamg::ell_span_pairs(gwruns, gwin, sgroup, kEllW, std::min(cap, pamg::kEllSpanWin), pamg::kEllSpanChunks,
+                                 pamg::kEllSpanShare);
+        E.npairs = (int)prs.size();
+        if (E.npairs > 0) {
+            std::vector<int> order;
+            std::vector<char> paired(ng, 0);
+            order.reserve(ng);
+            for (const auto& pr : prs) {
+                order.push_back(pr.first);
+                order.push_back(pr.second);
+                paired[pr.first] = paired[pr.second] = 1;
+            }
+            for (int64_t g = 0; g < ng; ++g)
+                if (!paired[g]) order.push_back((int)g);
+            auto permute = [&](auto& v) {
+                std::remove_reference_t<decltype(v)> t(v.size());
+                for (int64_t g = 0; g < ng; ++g) t[g] = std::move(v[order[g]]);
+                v.swap(t);
+            };
+            permute(grp);
+            permute(goff);
+            permute(gval);
+            permute(gchunk);
+            permute(glof);
+            permute(gwin);
+            permute(gwruns);
+            permute(glmin);
+            std::vector<int> usz(E.npairs);
+            int64_t usum = 0, upct = 0;
+            par_for(E.npairs, [&](int64_t a, int64_t b) {
+                pamg::EllRuns uni;
+                for (int64_t p = a; p < b; ++p) {
+                    int nch = 0;
+                    usz[p] = pamg::ell_span_union(gwruns[2 * p], gwruns[2 * p + 1], uni, nch);
+                    gchunk[2 * p].clear();
+                    gchunk[2 * p + 1].clear();
+                    for (const auto& r : uni)
+                        for (int c = r[0]; c < r[1]; c += 128)
+                            gchunk[2 * p].push_back(make_int2(c, (r[2] + c - r[0]) | (std::min(128, r[1] - c) / 2) << 16));
+                    for (int64_t g = 2 * p; g < 2 * p + 2; ++g) {
+                        for (size_t e = 0; e < glof[g].size(); ++e)  // (255: no lane of the wave reads the pair)
+                            if (glmin[g][e] != 255)
+                                glof[g][e] = pamg::ell_span_relof(glof[g][e], glmin[g][e], gwruns[g], uni);
+                        gunion[g] = usz[p];
+                    }
+                }
+            });
+            for (int p = 0; p < E.npairs; ++p) {
+                usum += usz[p];
+                upct += (int64_t)usz[p] * 100 / (gwin[2 * p] + gwin[2 * p + 1]);
+                E.max_union = std::max(E.max_union, usz[p]);
+            }
+            std::sort(usz.begin(), usz.end());
+            E.p95_union = usz[(usz.size() - 1) * 95 / 100];
+            E.mean_union = (int)(usum / E.npairs);
+            E.union_pct = (int)(upct / E.npairs);
+        }
+        std::vector<pamg::EllRuns>().swap(gwruns);
+        std::vector<std::vector<uint8_t>>().swap(glmin);
+    }
     std::vector<int4> gmeta(ng), wmeta(ng), gsl(ng);
     int64_t on = 0, cn = 0, ln = 0;
     for (int64_t g = 0; g < ng; ++g) {
         const int np = (int)goff[g].size();
         gmeta[g] = make_int4((int)on, np, (int)on, np);
-        wmeta[g] = make_int4((int)cn, (int)gchunk[g].size(), (int)ln, gwin[g]);
+        // (a paired group: .y 0 — alone, where x is not 16-byte aligned, it gathers — and .w its pair's window)
+        wmeta[g] = make_int4((int)cn, gunion[g] ? 0 : (int)gchunk[g].size(), (int)ln, gunion[g] ? gunion[g] : gwin[g]);
         gsl[g] = make_int4(grp[g][0], grp[g][1], grp[g][2], grp[g][3]);
         on += np;
         cn += (int64_t)gchunk[g].size();
@@ -1099,6 +1183,14 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     if (ln >= INT32_MAX || cn >= INT32_MAX) {
         E = pamg::EllSet{};
         return PAMG_OK;
+    }
+    std::vector<int4> prec((size_t)4 * E.npairs);
+    for (int p = 0; p < E.npairs; ++p) {
+        const int a = 2 * p, b = a + 1;
+        prec[4 * p] = gsl[a];
+        prec[4 * p + 1] = gsl[b];
+        prec[4 * p + 2] = make_int4(gmeta[a].x, gmeta[a].y, gmeta[b].x, gmeta[b].y);
+        prec[4 * p + 3] = make_int4(wmeta[a].x, (int)gchunk[a].size() | gunion[a] << 16, wmeta[a].z, wmeta[b].z);
     }
     std::vector<int> otab(on + 1, 0);
     std::vector<double> vtab(on + 1, 0.0);
@@ -1112,7 +1204,7 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
             std::copy(glof[g].begin(), glof[g].end(), lof.begin() + wmeta[g].z);
         }
     });
-    // Row classes (Options::ell_xwin 1 — 2 keeps the per-row stream —, EllSet::cls): the rows of a slice in classes of equal length,
+    // Row classes (Options::ell_xwin 1 | 3 — 2 | 4 keep the per-row stream —, EllSet::cls): the rows of a slice in classes of equal length,
     // diagonal position and pair bytes (the stream's padding bytes are 0, so equal dwords and equal
     // lengths are equal rows), numbered by first appearance; the slice then stores one padded row per
     // class, class-interleaved, and a class byte per row. Taken where that is at most half of the
@@ -1120,7 +1212,7 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     std::vector<int2> smeta_c;
     std::vector<uint32_t> ccw;
     std::vector<uint8_t> cid;
-    if (pamg::options().ell_xwin == 1) {
+    if (pamg::options().ell_xwin == 1 || pamg::options().ell_xwin == 3) {
         std::vector<int> snc(ns, 0), smin(ns, 0);
         cid.assign(n + kVecPad, 0);
         par_for(ns, [&](int64_t a, int64_t b) {
@@ -1215,6 +1307,10 @@ int build_ell_xwin(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     CHECK(h2d(ctx, E.d_wmeta, wmeta.data(), sizeof(int4) * ng));
     CHECK(h2d(ctx, E.d_chunks, chunks.data(), sizeof(int2) * (cn + 1)));
     CHECK(h2d(ctx, E.d_lof, lof.data(), sizeof(uint16_t) * (ln + 2)));
+    if (E.npairs > 0) {
+        CHECK(dalloc(&E.d_pairs, prec.size()));
+        CHECK(h2d(ctx, E.d_pairs, prec.data(), sizeof(int4) * prec.size()));
+    }
     A->interior.ell = true;
     return PAMG_OK;
 }
@@ -1463,7 +1559,9 @@ int64_t ell_bytes(const pamg_mat* A) {
     const int64_t index = A->ell.cls ? 4 * A->ell.cls_words + nrows : (A->ell.paired ? 4 : 8) * A->ell.words;
     return index + nrows + 8 * A->ell.nslices + 16 * A->ell.ngroups + 4 * A->ell.otab_n +
            8 * A->ell.vtab_n + (A->ell.d_anc ? 4 * nrows : 0) +
-           (A->ell.win ? 32 * A->ell.ngroups + 8 * A->ell.nchunks + 2 * A->ell.lof_n + nrows : 0);
+           (A->ell.win ? 32 * A->ell.ngroups + 8 * A->ell.nchunks + 2 * A->ell.lof_n + nrows : 0) -
+           // (a pair's workgroup reads its 64-byte record in place of two groups' 48 bytes of descriptors)
+           32 * (int64_t)A->ell.npairs;
 }
 
 void ell_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
@@ -1490,6 +1588,19 @@ void ell_window(const pamg_mat* A, int out[16]) {
     out[12] = w ? E.mean_pairs : 0;
     out[13] = w ? E.full_groups : 0;
     out[14] = out[15] = 0;
+}
+
+// the group pairs of a windowed operator (pamg_mat_ell_span)
+void ell_span(const pamg_mat* A, int out[8]) {
+    const pamg::EllSet& E = A->ell;
+    const bool w = A->interior.ell && E.win;
+    out[0] = w ? E.npairs : 0;
+    out[1] = w ? E.win_groups - 2 * E.npairs : 0;
+    out[2] = w ? E.mean_union : 0;
+    out[3] = w ? E.p95_union : 0;
+    out[4] = w ? E.union_pct : 0;
+    out[5] = w ? E.max_union : 0;
+    out[6] = out[7] = 0;
 }
 
 // the row classes of a windowed operator (pamg_mat_ell_classes)
@@ -1522,6 +1633,7 @@ void ell_free(pamg::EllSet& E) {
     dfree(E.d_chunks);
     dfree(E.d_lof);
     dfree(E.d_dpos);
+    dfree(E.d_pairs);
     E = pamg::EllSet{};
 }
 
@@ -3050,6 +3162,12 @@ int pamg_mat_layout(const pamg_mat* A, int set, int out[10]) {
 int pamg_mat_ell_window(const pamg_mat* A, int out[16]) {
     if (!A || !out) return fail(PAMG_E_ARG, "mat_ell_window: bad args");
     ell_window(A, out);
+    return PAMG_OK;
+}
+
+int pamg_mat_ell_span(const pamg_mat* A, int out[8]) {
+    if (!A || !out) return fail(PAMG_E_ARG, "mat_ell_span: bad args");
+    ell_span(A, out);
     return PAMG_OK;
 }
 

@@ -164,7 +164,9 @@ struct Options {
                                //    window entry are >= kEllWinMinRatio100 / 100 (below: the thresholds). With 1
                                //    a windowed operator also stores each slice's distinct rows once, and a class
                                //    byte per row, where that at least halves its index bytes (EllSet::cls);
-                               //    2: windowed, always the per-row index stream
+                               //    2: windowed, always the per-row index stream. With 1 and 2 windowed groups whose
+                               //    windows overlap are coupled into pairs that share one workgroup and one staged
+                               //    window (EllSet::npairs; k_rows_ellw's SPAN 2); 3 and 4: as 1 and 2 without pairs
     int ell_xwin_max = 7168;   // window capacity in doubles (<= kEllWinCap, the kernel's: 56 KB of its 60 KB of LDS)
     int pnc_compact = 1;       // 1: 16-bit combination ids instead of 64-bit records where <= kPncCombMax fit
     int pnc = 1;               // != 0: neighbour-coded prolongations over a grid registered on the context (PncSet);
@@ -225,6 +227,21 @@ constexpr int kEllLdsPerCu = 160 * 1024;
 constexpr int kEllWinKeep = 85;  // percent of the windowed groups kept when the largest window is lowered for occupancy
 constexpr int kEllWinMinShare = 50;
 constexpr int kEllWinMinRatio100 = 150;
+// Group pairs (Options::ell_xwin 1 and 2, not 3 and 4; ell_span.h, k_rows_ellw's SPAN 2): two windowed groups whose
+// windows overlap run in one workgroup of 2 * kEllGroup threads behind one barrier, their union
+// window staged once. The groups are renumbered so that pair p holds groups 2p and 2p + 1 and the
+// groups left single follow; d_pairs holds 4 int4 per pair: the slices of group 2p, of group 2p + 1,
+// (table start and entries of either), (first chunk, chunks | window doubles << 16, first d_lof word
+// of either). A CU holds 2,048 threads, so at most 4 such workgroups, whatever their LDS; fewer would
+// be the single groups' 24 waves or less. So the union's capacity is what 4 per CU leave of the LDS
+// after either group's tables (2 x 4 KB): kEllSpanWin doubles. 8 waves read the chunk words, lane k
+// of wave w chunk w + 8k: kEllSpanChunks. A pair is kept where the union is at most kEllSpanShare
+// percent of the two windows together: the workgroup's barrier waits for the whole union, the longer
+// staging chain of the two, and that is paid for by what is staged less — below a tenth of two
+// windows (~600 doubles at 512^3) the saving is less than one group's tables and lof words (4 KB).
+constexpr int kEllSpanWin = (kEllLdsPerCu / 4 - 2 * 4096) / 8;
+constexpr int kEllSpanChunks = 2 * kEllWinChunks;
+constexpr int kEllSpanShare = 90;
 struct EllSet {
     int64_t nslices = 0, ngroups = 0;
     int2* d_smeta = nullptr;     // per slice: (first dword of its index streams, maxlen)
@@ -246,7 +263,8 @@ struct EllSet {
     // windowed (Options::ell_xwin; then paired, d_anc and d_gorder null, ngroups = the coupled groups)
     bool win = false;
     int4* d_gslices = nullptr;   // per group: its waves' slices (-1: none)
-    int4* d_wmeta = nullptr;     // per group: (first chunk, chunks — 0: gather —, first d_lof word, window doubles)
+    int4* d_wmeta = nullptr;     // per group: (first chunk, chunks — 0: gather —, first d_lof word, window doubles);
+                                 // a paired group: chunks 0 (alone it gathers), window = its pair's union
     int2* d_chunks = nullptr;
     uint16_t* d_lof = nullptr;
     uint8_t* d_dpos = nullptr;
@@ -255,7 +273,12 @@ struct EllSet {
     int max_window = 0, max_pairs = 0, max_chunks = 0;  // over the windowed groups (max_pairs: all groups)
     // census of the upload (pamg_mat_ell_window): windows, runs and pairs per windowed group, 4-slice groups
     int mean_window = 0, p95_window = 0, mean_runs = 0, max_runs = 0, mean_pairs = 0, full_groups = 0;
-    // row classes (Options::ell_xwin 1; windowed operators): two rows of a slice are one class where their
+    // group pairs (Options::ell_xwin 1 | 2; above): groups 0 .. 2 npairs - 1 run pairwise, the rest alone
+    int4* d_pairs = nullptr;
+    int npairs = 0;
+    int max_union = 0, mean_union = 0, p95_union = 0;  // the pairs' union windows (doubles)
+    int union_pct = 0;                                  // mean of union / (the two windows), percent
+    // row classes (Options::ell_xwin 1 | 3; windowed operators): two rows of a slice are one class where their
     // length, diagonal position and pair bytes are equal. d_ci then holds every slice's classes once, padded
     // to the slice's dwords and class-interleaved — dword q of class c at start + q * nc + c, d_smeta .y =
     // maxlen | minlen << 8 | nc << 16 (minlen: the slice's shortest row, 0 for a partial slice: the dwords

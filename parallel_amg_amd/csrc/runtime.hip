@@ -2531,7 +2531,7 @@ const OptionRow kOptionTable[] = {
     {"rpat", &O::rpat, 0, 1, false},
     {"pnc_compact", &O::pnc_compact, 0, 1, false},
     {"ell_pair", &O::ell_pair, 0, 1, false},
-    {"ell_xwin", &O::ell_xwin, 0, 2, false},  // 1 with row classes where they pay, 2 without
+    {"ell_xwin", &O::ell_xwin, 0, 4, false},  // 1 with row classes where they pay, 2 without; 3, 4: as 1, 2 without group pairs
     {"ell_xwin_max", &O::ell_xwin_max, 2, pamg::kEllWinCap, false},
     {"ell_yblock", &O::ell_yblock, 0, 65536, false},
     {"ell_min_rows", &O::ell_min_rows, 0, INT32_MAX, false},
