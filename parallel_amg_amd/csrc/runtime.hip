@@ -17,13 +17,17 @@
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <utility>
 #include <vector>
 
+#include "cycle_plan.h"
 #include "pamg_device.h"
 #include "pamg_host.h"
+
+namespace plan = pamg::plan;
 
 pamg::Options& pamg::options() {
     static Options o;
@@ -394,25 +398,34 @@ void cheb_coeffs(double lmax, double ratio, int m, double* c1, double* c2) {
     }
 }
 
-// One Chebyshev polynomial of degree m on level operator A (SPEC §S9). in: x_0, or null for a zero
-// guess (step 0 is then the zero-guess Jacobi form and step 1 passes a null xold). The iterates
-// rotate through ring[0..2] — x_1 into ring[0], x_2 into ring[1], ... — three distinct vectors none
-// of which is `in` or b unless the caller knows `in` dead by then: step k writes ring[k % 3], reads
-// x_k = ring[(k - 1) % 3] and x_{k-1} = ring[(k - 2) % 3] (k = 1: in), so y never aliases x or
-// xold. Returns the vector holding x_m.
-// block: the steps in point-block form (SPEC §S12; A carries block data), else §S9's.
-int cheb_poly(pamg_ctx* ctx, const pamg_mat* A, int64_t nown, const double* c1, const double* c2, int m, double* in,
-              const double* b, double* const ring[3], double** out, bool block = false) {
-    hipStream_t s = ctx->s_comp;
-    if (block) CHECK(block_step(ctx, A, in ? pamg::BM_JACOBI : pamg::BM_ZERO, in, b, nullptr, ring[0], 0.0, c2[0]));
-    else if (in) CHECK(apply(ctx, A, pamg::OP_JACOBI, in, b, ring[0], c2[0]));
-    else pamg::launch_jacobi_zero(nown, b, A->d_diag, c2[0], ring[0], s);
-    for (int k = 1; k < m; ++k) {
-        const double* xo = k == 1 ? in : ring[(k - 2) % 3];
-        if (block) CHECK(block_step(ctx, A, pamg::BM_CHEB, ring[(k - 1) % 3], b, xo, ring[k % 3], c1[k], c2[k]));
-        else CHECK(apply(ctx, A, pamg::OP_CHEB, ring[(k - 1) % 3], b, ring[k % 3], c2[k], c1[k], xo));
+// One smoothing step of a plan (cycle_plan.h) on level operator A: the only place that chooses between
+// the scalar (SPEC §S3, §S9) and the point-block form (§S12; blk: A carries block data) and among the
+// zero-guess, Jacobi and Chebyshev forms. c2 is the Jacobi weight, or the Chebyshev step's c2 with c1
+// (0 outside OP_CHEB); in and xold are null where the step names none.
+int smooth_step(pamg_ctx* ctx, const pamg_mat* A, bool blk, plan::Op op, double* in, const double* b, const double* xold,
+                double* out, double c1, double c2) {
+    if (blk) {
+        const int mode = op == plan::CHEB ? pamg::BM_CHEB : op == plan::SMOOTH ? pamg::BM_JACOBI : pamg::BM_ZERO;
+        return block_step(ctx, A, mode, in, b, xold, out, c1, c2);
     }
-    *out = ring[(m - 1) % 3];
+    if (op == plan::CHEB) return apply(ctx, A, pamg::OP_CHEB, in, b, out, c2, c1, xold);
+    if (op == plan::SMOOTH) return apply(ctx, A, pamg::OP_JACOBI, in, b, out, c2);
+    pamg::launch_jacobi_zero(A->nrows, b, A->d_diag, c2, out, ctx->s_comp);
+    return PAMG_OK;
+}
+
+// One Chebyshev polynomial of degree m from x_0 = x on operator A (SPEC §S9; block: §S12's form), the
+// iterates rotating through t1, t2 and x as plan_poly lays out (x_0 is free again from step 2 on).
+// *out: the vector holding x_m.
+int cheb_poly(pamg_ctx* ctx, const pamg_mat* A, const double* c1, const double* c2, int m, double* x, const double* b,
+              double* t1, double* t2, double** out, bool block) {
+    double* const vec[5] = {x, const_cast<double*>(b), t1, t2, nullptr};  // by role
+    const plan::Role ring[3] = {plan::T, plan::R, plan::X};
+    std::vector<plan::Step> steps;
+    *out = vec[plan::plan_poly(m, plan::X, ring, 0, 0, steps)];
+    for (const plan::Step& st : steps)
+        CHECK(smooth_step(ctx, A, block, st.op, vec[st.in], vec[plan::B], st.xold == plan::NONE ? nullptr : vec[st.xold],
+                          vec[st.out], c1[st.k], c2[st.k]));
     return PAMG_OK;
 }
 
@@ -725,14 +738,13 @@ struct ProfScope {
 // One V-cycle (SPEC §S6), enqueued on the compute stream; result in x. zero0: the level-0
 // initial guess is zero (preconditioner use), so the level-0 pre-smoothing takes the
 // zero-guess form too (bit-identical to the full sweep from x = 0, SPEC §S3).
-// Level-0 segments of the cross-cycle pipeline (vcycle_raw): l0_given — the level-0 pre-smoothed
-// iterate and residual are already in t0 / r0 (a k_sym_chain launch made them); l0_post —
-// whether this call ends with the level-0 post-smoothing (else the prolongated t0 is left for
-// the next chain launch). Defaults: one whole cycle.
+// Level-0 segments of the cross-cycle pipeline (vcycle_raw): given — the level-0 pre-smoothed
+// iterate and residual are already in t0 (t[0] or u0) and r[0] (a k_sym_chain launch made them);
+// post — whether this call ends with the level-0 post-smoothing (else the prolongated t0 is left
+// for the next chain launch). Defaults: one whole cycle.
 struct L0Seg {
     bool given = false;
-    double* t0 = nullptr;
-    double* r0 = nullptr;
+    plan::Role t0 = plan::T;
     bool post = true;
 };
 
@@ -745,6 +757,29 @@ bool block_level(const pamg_hier* H, int l) {
            H->A[l]->bs > 1;
 }
 
+// The coefficients of smoothing step k on level l: the Jacobi weight, or the level's Chebyshev c1 / c2
+void smooth_coeffs(const pamg_hier* H, int l, int k, double* c1, double* c2) {
+    *c1 = cheb_kind(H) ? H->cheb_c1[l][k] : 0.0;
+    *c2 = cheb_kind(H) ? H->cheb_c2[l][k] : H->omega[l];
+}
+
+// What the planner needs to know of this hierarchy and call (cycle_plan.h)
+plan::CycleSpec cycle_spec(const pamg_hier* H, bool zero0, const L0Seg& seg = L0Seg{}) {
+    plan::CycleSpec sp;
+    sp.L = H->L;
+    sp.nu1 = H->nu1;
+    sp.nu2 = H->nu2;
+    sp.cheb = cheb_kind(H);
+    sp.zero0 = zero0;
+    // level 0, V(1, nu2) from a given guess: the pre-smoothing sweep and the residual in one temporally
+    // blocked pass where the operator has one (jacobi_residual; both timed as jacobi_pre)
+    sp.l0_fused = H->smoother == PAMG_SMOOTHER_JACOBI && !zero0 && !seg.given && H->nu1 == 1 && jr_blocked(H->A[0]) != 0;
+    sp.l0_given = seg.given;
+    sp.l0_t = seg.t0;
+    sp.l0_post = seg.post;
+    return sp;
+}
+
 int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false, L0Seg seg = L0Seg{}) {
     pamg_ctx* ctx = H->ctx;
     hipStream_t s = ctx->s_comp;
@@ -755,138 +790,79 @@ int vcycle_enqueue(pamg_hier* H, double* x, const double* b, bool zero0 = false,
     }
     H->x[0] = x;
     H->b[0] = const_cast<double*>(b);
-    // V(nu1, nu2): the pre-smoothed iterate of level l ends in t[l] or r[l] (sweeps
-    // ping-pong between them); the residual goes to the other one; the post-smoothing
-    // sweeps ping-pong between x[l] and the spare so that the last one writes x[l]
-    std::vector<double*> cur(L, nullptr), spare(L, nullptr);
-    // Chebyshev smoother (SPEC §S9): a polynomial's iterates rotate through three vectors (cheb_poly)
-    // — the level's x, t and r, the input x_0 being free again from step 2 on — so the post-smoothed
-    // iterate of a level >= 1 ends in whichever of them the degrees select (xres, read by the
-    // prolongation above it); on level 0 it must end in the caller's x, which the choice of the
-    // rings arranges (with the spare u0 where the two degrees' remainders mod 3 disagree, need_u0)
-    const bool cheb = cheb_kind(H);
-    const bool blocks = H->smoother == PAMG_SMOOTHER_BLOCK_JACOBI || H->smoother == PAMG_SMOOTHER_BLOCK_CHEBYSHEV;
-    std::vector<double*> xres(H->x);
-    auto others = [&](int l, const double* not_this, double* out[4]) {  // the level's vectors, x[l] last
-        int n = 0;
-        for (double* v : {H->t[l], H->r[l], l == 0 ? H->u0 : (double*)nullptr, H->x[l]})
-            if (v && v != not_this) out[n++] = v;
-        return n;
+    // which vector every step reads and writes is the plan's business (proved free of aliasing and
+    // stale reads by tools/cycle_plan_check.cpp); here the roles become pointers and the steps launches
+    const plan::CyclePlan cp = plan::plan_cycle(cycle_spec(H, zero0, seg));
+    if (cp.needs_u0 && !H->u0) return fail(PAMG_E_STATE, "vcycle: the cycle lacks its spare level-0 vector");
+    auto vec = [&](int l, plan::Role r) -> double* {
+        double* const v[5] = {H->x[l], H->b[l], H->t[l], H->r[l], H->u0};
+        return r == plan::NONE ? nullptr : v[r];
     };
-    for (int l = 0; l < L - 1; ++l) {
-        const pamg_mat* A = H->A[l];
-        double *c = H->t[l], *o = H->r[l];
-        if (l == 0 && seg.given) {  // made by the chain launch before this call
-            cur[0] = seg.t0;
-            spare[0] = seg.r0;
-            ProfScope p(H, 0, 2, s);
-            CHECK(apply(ctx, H->R[0], pamg::OP_SPMV, seg.r0, nullptr, H->b[1], 0.0));
-            continue;
+    std::optional<ProfScope> scope;  // one per run of steps with the same (level, slot)
+    const plan::Step* prev = nullptr;
+    for (const plan::Step& st : cp.steps) {
+        const int l = st.level;
+        if (!prev || prev->level != l || prev->slot != st.slot) {
+            scope.reset();
+            scope.emplace(H, l, st.slot, s);
         }
-        // level 0, V(1, nu2) from a given guess: the pre-smoothing sweep and the residual in one
-        // temporally blocked pass where the operator has one (jacobi_residual; both timed as
-        // jacobi_pre)
-        const bool fuse = !cheb && !blocks && l == 0 && !zero0 && H->nu1 == 1 && jr_blocked(A) != 0;
-        const bool blk = block_level(H, l);
-        if (cheb) {
-            ProfScope p(H, l, 0, s);
-            double* in = l == 0 && !zero0 ? H->x[0] : nullptr;
-            double* ring[3] = {H->t[l], H->r[l], H->x[l]};
-            const int last = (H->nu1 - 1) % 3;
-            if (l == 0) {
-                const bool want_x0 = H->nu2 % 3 == 0;  // the post-smoothing ring ends where it starts
-                if (in) {  // x[0] is x_0: ring[2] or nothing
-                    if (last == 2 && !want_x0) ring[2] = H->u0;
-                } else if (want_x0) {
-                    std::swap(ring[last], ring[2]);
-                } else if (last == 2) {
-                    std::swap(ring[0], ring[2]);
+        prev = &st;
+        double* in = vec(l, st.in);
+        double* out = vec(l, st.out);
+        switch (st.op) {
+            case plan::RESID:
+                CHECK(apply(ctx, H->A[l], pamg::OP_RESID, in, H->b[l], out, 0.0));
+                break;
+            case plan::JACOBI_RESID: {
+                bool fused = false;
+                CHECK(jacobi_residual(ctx, H->A[l], in, H->b[l], out, H->r[l], H->omega[l], &fused));
+                break;
+            }
+            case plan::RESTRICT:
+                if (l + 1 == H->rep && ctx->nranks > 1) {  // into the replicated tail
+                    CHECK(apply(ctx, H->R[l], pamg::OP_SPMV, in, nullptr, H->d_bsend, 0.0));
+                    CHECK(gather_rep(H, H->b[l + 1], s));
+                } else {
+                    CHECK(apply(ctx, H->R[l], pamg::OP_SPMV, in, nullptr, H->b[l + 1], 0.0));
                 }
-            }
-            if (!ring[2]) return fail(PAMG_E_STATE, "vcycle: the Chebyshev cycle lacks its spare level-0 vector");
-            CHECK(cheb_poly(ctx, A, H->nown[l], H->cheb_c1[l].data(), H->cheb_c2[l].data(), H->nu1, in, H->b[l], ring,
-                            &c, blk));
-            double* oth[4];
-            others(l, c, oth);
-            o = oth[0];
-        } else if (fuse) {
-            ProfScope p(H, l, 0, s);
-            bool fused = false;
-            CHECK(jacobi_residual(ctx, A, H->x[0], H->b[0], c, o, H->omega[0], &fused));
-        } else {
-            ProfScope p(H, l, 0, s);
-            if (blk)
-                CHECK(block_step(ctx, A, l == 0 && !zero0 ? pamg::BM_JACOBI : pamg::BM_ZERO, H->x[0], H->b[l], nullptr, c,
-                                 0.0, H->omega[l]));
-            else if (l == 0 && !zero0)
-                CHECK(apply(ctx, A, pamg::OP_JACOBI, H->x[0], H->b[0], c, H->omega[0]));
-            else
-                pamg::launch_jacobi_zero(H->nown[l], H->b[l], A->d_diag, H->omega[l], c, s);
-            for (int k = 1; k < H->nu1; ++k) {
-                if (blk) CHECK(block_step(ctx, A, pamg::BM_JACOBI, c, H->b[l], nullptr, o, 0.0, H->omega[l]));
-                else CHECK(apply(ctx, A, pamg::OP_JACOBI, c, H->b[l], o, H->omega[l]));
-                std::swap(c, o);
-            }
-        }
-        cur[l] = c;
-        spare[l] = o;
-        if (!fuse) {
-            ProfScope p(H, l, 1, s);
-            CHECK(apply(ctx, A, pamg::OP_RESID, c, H->b[l], o, 0.0));
-        }
-        {
-            ProfScope p(H, l, 2, s);
-            if (l + 1 == H->rep && ctx->nranks > 1) {  // into the replicated tail
-                CHECK(apply(ctx, H->R[l], pamg::OP_SPMV, o, nullptr, H->d_bsend, 0.0));
-                CHECK(gather_rep(H, H->b[l + 1], s));
-            } else {
-                CHECK(apply(ctx, H->R[l], pamg::OP_SPMV, o, nullptr, H->b[l + 1], 0.0));
+                break;
+            case plan::COARSE:
+                CHECK(coarse_solve(H, in, out, s));
+                break;
+            case plan::PROLONG:
+                CHECK(apply(ctx, H->P[l], pamg::OP_PROLONG, vec(l + 1, st.in), nullptr, out, 0.0));
+                break;
+            default: {
+                double c1, c2;
+                smooth_coeffs(H, l, st.k, &c1, &c2);
+                CHECK(smooth_step(ctx, H->A[l], block_level(H, l), st.op, in, H->b[l], vec(l, st.xold), out, c1, c2));
             }
         }
     }
-    {
-        ProfScope p(H, L - 1, 5, s);
-        CHECK(coarse_solve(H, H->b[L - 1], H->x[L - 1], s));
-    }
-    for (int l = L - 2; l >= 0; --l) {
-        {
-            ProfScope p(H, l, 3, s);
-            CHECK(apply(ctx, H->P[l], pamg::OP_PROLONG, xres[l + 1], nullptr, cur[l], 0.0));
-        }
-        if (l == 0 && !seg.post) break;
-        if (cheb) {
-            ProfScope p(H, l, 4, s);
-            double* oth[4];
-            const int no = others(l, cur[l], oth);
-            double* ring[3] = {oth[0], oth[1], cur[l]};
-            const int last = (H->nu2 - 1) % 3;
-            if (l == 0 && last == 2 && cur[0] != H->x[0]) {
-                if (no < 3) return fail(PAMG_E_STATE, "vcycle: the Chebyshev cycle lacks its spare level-0 vector");
-                ring[2] = H->x[0];  // (oth[0], oth[1]: t, r or u0)
-            } else if (l == 0 && last < 2) {
-                if (cur[0] == H->x[0]) return fail(PAMG_E_STATE, "vcycle: Chebyshev ring order");
-                ring[last] = H->x[0];
-                ring[1 - last] = oth[0];
-            }
-            CHECK(cheb_poly(ctx, H->A[l], H->nown[l], H->cheb_c1[l].data(), H->cheb_c2[l].data(), H->nu2, cur[l],
-                            H->b[l], ring, &xres[l], block_level(H, l)));
-            if (l == 0 && xres[0] != H->x[0]) return fail(PAMG_E_STATE, "vcycle: Chebyshev ring order");
-        } else {
-            ProfScope p(H, l, 4, s);
-            double* in = cur[l];
-            for (int k = 0; k < H->nu2; ++k) {
-                double* out = ((H->nu2 - k) % 2 == 1) ? H->x[l] : spare[l];
-                if (block_level(H, l))
-                    CHECK(block_step(ctx, H->A[l], pamg::BM_JACOBI, in, H->b[l], nullptr, out, 0.0, H->omega[l]));
-                else
-                    CHECK(apply(ctx, H->A[l], pamg::OP_JACOBI, in, H->b[l], out, H->omega[l]));
-                if (out == spare[l]) spare[l] = in;
-                in = out;
-            }
-        }
-    }
+    scope.reset();
     HIPC(hipGetLastError());
     return PAMG_OK;
+}
+
+// Capture what enqueue() puts on stream s into *exec (thread-local mode: other host threads go on
+// launching). False if any step fails; *exec is then not to be used.
+template <class F>
+bool capture_graph(hipStream_t s, F&& enqueue, hipGraphExec_t* exec) {
+    hipGraph_t g = nullptr;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
+    const int rc = enqueue();
+    const hipError_t e2 = hipStreamEndCapture(s, &g);
+    const bool ok = rc == PAMG_OK && e2 == hipSuccess && g && hipGraphInstantiate(exec, g, nullptr, nullptr, 0) == hipSuccess;
+    if (g) (void)hipGraphDestroy(g);
+    return ok;
+}
+
+// A failed capture sends the hierarchy to eager launches of the same kernels for good.
+void capture_failed(pamg_hier* H, const char* what) {
+    (void)hipGetLastError();
+    H->use_graph = false;
+    H->graph_failed = true;
+    fprintf(stderr, "[pamg] %s graph capture failed (%s); using eager launches\n", what, pamg::last_error().c_str());
 }
 
 }  // namespace
@@ -1805,9 +1781,8 @@ int pamg_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec
     if (b->n_own != A->nrows || tmp1 == x || tmp2 == x || tmp1 == tmp2 || b == x || b == tmp1 || b == tmp2)
         return fail(PAMG_E_ARG, "chebyshev: size mismatch or aliasing");
     CHECK(set_device(ctx));
-    double* ring[3] = {tmp1->d, tmp2->d, x->d};  // (x is x_0: free again from step 2 on)
     double* res = nullptr;
-    CHECK(cheb_poly(ctx, A, A->nrows, c1, c2, degree, x->d, b->d, ring, &res));
+    CHECK(cheb_poly(ctx, A, c1, c2, degree, x->d, b->d, tmp1->d, tmp2->d, &res, false));
     if (res != x->d)
         HIPC(hipMemcpyAsync(x->d, res, sizeof(double) * x->n_own, hipMemcpyDeviceToDevice, ctx->s_comp));
     HIPC(hipStreamSynchronize(ctx->s_comp));
@@ -1859,7 +1834,7 @@ int pamg_block_jacobi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_
     double* cur = x->d;
     double* nxt = tmp->d;
     for (int k = 0; k < nsweeps; ++k) {
-        CHECK(block_step(ctx, A, pamg::BM_JACOBI, cur, b->d, nullptr, nxt, 0.0, omega));
+        CHECK(smooth_step(ctx, A, true, plan::SMOOTH, cur, b->d, nullptr, nxt, 0.0, omega));
         std::swap(cur, nxt);
     }
     if (cur != x->d)
@@ -1880,9 +1855,8 @@ int pamg_block_chebyshev(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pa
     if (b->n_own != A->nrows || tmp1 == x || tmp2 == x || tmp1 == tmp2 || b == x || b == tmp1 || b == tmp2)
         return fail(PAMG_E_ARG, "block_chebyshev: size mismatch or aliasing");
     CHECK(set_device(ctx));
-    double* ring[3] = {tmp1->d, tmp2->d, x->d};
     double* res = nullptr;
-    CHECK(cheb_poly(ctx, A, A->nrows, c1, c2, degree, x->d, b->d, ring, &res, true));
+    CHECK(cheb_poly(ctx, A, c1, c2, degree, x->d, b->d, tmp1->d, tmp2->d, &res, true));
     if (res != x->d)
         HIPC(hipMemcpyAsync(x->d, res, sizeof(double) * x->n_own, hipMemcpyDeviceToDevice, ctx->s_comp));
     HIPC(hipStreamSynchronize(ctx->s_comp));
@@ -2014,8 +1988,7 @@ static int pipe_enqueue(pamg_hier* H, double* x, const double* b, int seg) {
             CHECK(launch_chain3(H, x, b, prev, next));
         }
         sg.given = true;
-        sg.t0 = next;
-        sg.r0 = H->r[0];
+        sg.t0 = seg == 1 ? plan::U0 : plan::T;
         return vcycle_enqueue(H, x, b, false, sg);
     }
     ProfScope p(H, 0, 4, H->ctx->s_comp);
@@ -2058,27 +2031,14 @@ static int vcycle_pipe(pamg_hier* H, double* x, const double* b, int ncycles) {
         drop_pipe_graphs(H);
         bool ok = true;
         hipGraphExec_t* slot[5] = {&H->g_head, &H->g_steady[0], &H->g_steady[1], &H->g_tail[0], &H->g_tail[1]};
-        for (int sgi = 0; sgi < 5 && ok; ++sgi) {
-            hipGraph_t g = nullptr;
-            if (hipStreamBeginCapture(ctx->s_comp, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                ok = false;
-                break;
-            }
-            const int rc = pipe_enqueue(H, x, b, sgi);
-            const hipError_t e2 = hipStreamEndCapture(ctx->s_comp, &g);
-            ok = rc == PAMG_OK && e2 == hipSuccess && g && hipGraphInstantiate(slot[sgi], g, nullptr, nullptr, 0) == hipSuccess;
-            if (g) (void)hipGraphDestroy(g);
-        }
+        for (int sgi = 0; sgi < 5 && ok; ++sgi)
+            ok = capture_graph(ctx->s_comp, [&] { return pipe_enqueue(H, x, b, sgi); }, slot[sgi]);
         if (ok) {
             H->gp_x = x;
             H->gp_b = b;
         } else {
-            (void)hipGetLastError();
+            capture_failed(H, "pipelined V-cycle");
             drop_pipe_graphs(H);
-            H->use_graph = false;
-            H->graph_failed = true;
-            fprintf(stderr, "[pamg] pipelined V-cycle graph capture failed (%s); using eager launches\n",
-                    pamg::last_error().c_str());
         }
     }
     for (int k = 0; k <= K; ++k) {
@@ -2098,39 +2058,21 @@ static int vcycle_raw(pamg_hier* H, double* x, const double* b, int ncycles, boo
     if (zero0 && ncycles != 1) return fail(PAMG_E_ARG, "vcycle: zero initial guess applies to one cycle");
     // stationary runs of >= 2 cycles: the cross-cycle pipeline (same operations, same bits)
     if (pipe_ok(H, ncycles, zero0)) return vcycle_pipe(H, x, b, ncycles);
-    // Chebyshev from a given guess: level 0's rings need a fourth vector where exactly one of the two
-    // degrees is a multiple of 3 (vcycle_enqueue); allocated before any capture
-    if ((H->smoother == PAMG_SMOOTHER_CHEBYSHEV || H->smoother == PAMG_SMOOTHER_BLOCK_CHEBYSHEV) && H->L > 1 && !zero0 &&
-        (H->nu1 % 3 == 0) != (H->nu2 % 3 == 0))
-        CHECK(ensure_u0(H));
+    // the spare level-0 vector where the plan names it, allocated before any capture
+    if (H->L > 1 && !H->u0 && plan::plan_cycle(cycle_spec(H, zero0)).needs_u0) CHECK(ensure_u0(H));
     if (H->use_graph && !H->prof && (!H->gexec || H->g_x != x || H->g_b != b || H->g_zero0 != zero0)) {
         // Capture one cycle (RCCL exchanges included on several parts: RCCL records its
         // send/recv/all-gather as graph nodes). If capture fails, fall back to eager launches
         // for this hierarchy: both paths issue the same RCCL sequence, so ranks that did
         // capture and ranks that did not still match.
         drop_cycle_graph(H);
-        hipGraph_t g = nullptr;
-        int rc = PAMG_OK;
-        hipError_t e1 = hipStreamBeginCapture(ctx->s_comp, hipStreamCaptureModeThreadLocal);
-        if (e1 == hipSuccess) {
-            rc = vcycle_enqueue(H, x, b, zero0);
-            hipError_t e2 = hipStreamEndCapture(ctx->s_comp, &g);
-            if (rc == PAMG_OK && e2 == hipSuccess && g &&
-                hipGraphInstantiate(&H->gexec, g, nullptr, nullptr, 0) == hipSuccess) {
-                H->g_x = x;
-                H->g_b = b;
-                H->g_zero0 = zero0;
-            } else {
-                H->gexec = nullptr;
-            }
-            if (g) (void)hipGraphDestroy(g);
-        }
-        if (!H->gexec) {
-            (void)hipGetLastError();
-            H->use_graph = false;
-            H->graph_failed = true;
-            fprintf(stderr, "[pamg] V-cycle graph capture failed (%s); using eager launches\n",
-                    pamg::last_error().c_str());
+        if (capture_graph(ctx->s_comp, [&] { return vcycle_enqueue(H, x, b, zero0); }, &H->gexec)) {
+            H->g_x = x;
+            H->g_b = b;
+            H->g_zero0 = zero0;
+        } else {
+            H->gexec = nullptr;
+            capture_failed(H, "V-cycle");
         }
     }
     if (H->use_graph && !H->prof && H->gexec) {
@@ -2333,28 +2275,14 @@ void pcg_capture(pamg_hier* H, double* xd) {
     pamg_ctx* ctx = H->ctx;
     drop_pcg_graphs(H);
     bool ok = true;
-    for (int half = 0; half < 2 && ok; ++half) {
-        hipGraph_t g = nullptr;
-        if (hipStreamBeginCapture(ctx->s_comp, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            ok = false;
-            break;
-        }
-        const int rc = pcg_half_enqueue(H, xd, half);
-        const hipError_t e2 = hipStreamEndCapture(ctx->s_comp, &g);
-        ok = rc == PAMG_OK && e2 == hipSuccess && g &&
-             hipGraphInstantiate(&H->g_pcg[half], g, nullptr, nullptr, 0) == hipSuccess;
-        if (g) (void)hipGraphDestroy(g);
-    }
+    for (int half = 0; half < 2 && ok; ++half)
+        ok = capture_graph(ctx->s_comp, [&] { return pcg_half_enqueue(H, xd, half); }, &H->g_pcg[half]);
     if (ok) {
         H->gr_x = xd;
         return;
     }
-    (void)hipGetLastError();
+    capture_failed(H, "PCG iteration");
     drop_pcg_graphs(H);
-    H->use_graph = false;
-    H->graph_failed = true;
-    fprintf(stderr, "[pamg] PCG iteration graph capture failed (%s); using eager launches\n",
-            pamg::last_error().c_str());
 }
 
 }  // namespace

@@ -21,6 +21,7 @@ from parallel_amg_amd._lib import PamgError, call, layout_of
 from parallel_amg_amd.partitioned import (LocalWorld, PSparseMatrix, PVector, block_chebyshev, block_jacobi,
                                           estimate_lmax_block, mul)
 from parallel_amg_amd.solver import AMGSolver
+from test_gpu_chebyshev import PAIRS, pcg_bits_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -399,6 +400,38 @@ def test_pcg(ctx, name, kind, nu):
     assert k0 == k
     assert np.array_equal(bits(x0.own_values()), bits(x.own_values()))
     assert np.array_equal(bits(hist0), bits(hist))
+
+
+@pytest.mark.parametrize("nu", PAIRS)
+@pytest.mark.parametrize("kind", ["jacobi", "chebyshev"])
+def test_cycle_and_pcg_bits_every_pair(ctx, kind, nu):
+    """elastic3d 8, every (nu1, nu2) in {1..4}^2 (the sweeps' ping-pong parities, the degrees' remainders
+    mod 3): 2 stationary cycles from a given guess, graph and eager, give the restatement's x bits; 2
+    PCG iterations (every cycle from a zero guess) the restated iteration's x and history bits."""
+    S, b, bo, refs, cache = problem(ctx, "elastic3d8")
+    ref = refs[kind]
+    if ("two", kind, nu) not in cache:
+        cache[("two", kind, nu)] = (ref.solve(bo, 2, *nu),
+                                    pcg_bits_ref(lambda r: ref.cycle(0, None, r, *nu), ref.H.A[0], bo, 2))
+    (xo, ho), (xp, hp) = cache[("two", kind, nu)]
+    with smoother(S, "block_" + kind, nu, ratio=4.0):
+        for graph in (True, False):
+            S.set_graph(graph)
+            x = S.new_vector()
+            hist = S.vcycle(x, b, 2, res_hist=True)
+            got = bits(x.own_values())
+            assert np.array_equal(got, bits(xo)), (kind, nu, graph, differ(got, bits(xo)))
+            np.testing.assert_allclose(hist, ho, rtol=1e-12)
+            assert S.graph_state()["captured"] == graph
+            assert not S.graph_state()["failed"]
+        S.set_graph(True)
+        for lookahead in (None, 0):
+            x = S.new_vector()
+            k, hist = S.pcg(x, b, 0.0, 2, lookahead=lookahead)
+            got = bits(x.own_values())
+            assert k == 2
+            assert np.array_equal(got, bits(xp)), (kind, nu, lookahead, differ(got, bits(xp)))
+            assert np.array_equal(bits(hist), bits(hp)), (kind, nu, lookahead)
 
 
 def test_switching_back_leaves_no_state(ctx):

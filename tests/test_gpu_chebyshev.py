@@ -415,7 +415,7 @@ def problem(ctx, name):
         Ho = O.setup(Ao, max_coarse=mc)
         assert Ho.nlevels == H.nlevels
         assert [H.levels[l][0].rho for l in range(H.nlevels)] == list(Ho.rho)
-        _problems[name] = (S, b, bo, Ho, CycleRef(Ho), {})
+        _problems[name] = (S, b, bo, Ho, CycleRef(Ho), {"hierarchy": H})
     return _problems[name]
 
 
@@ -454,6 +454,104 @@ def test_cycle_bits(ctx, name, nu):
         S.set_graph(True)
         S.set_smoother("jacobi")
         S.set_sweeps(1, 1)
+
+
+# Every remainder of the two degrees mod 3 (the polynomial's iterates rotate through three vectors), on
+# both sides of the spare vector's rule: it is needed where exactly one degree is a multiple of 3.
+PAIRS = [(nu1, nu2) for nu1 in (1, 2, 3, 4) for nu2 in (1, 2, 3, 4)]
+
+
+def pcg_bits_ref(cycle, A, b, maxit):
+    """maxit iterations of SPEC §S8 from x = 0 (no convergence test) in the device's arithmetic: the dots
+    as test_gpu_reductions restates them, the updates rounded as axpby rounds them, z = cycle(r) from a
+    zero guess. Returns x and the history of ||r||."""
+    from test_gpu_reductions import restated_dot
+    x = np.zeros(len(b))
+    r = O.residual(A, x, b)
+    hist = [np.sqrt(np.float64(restated_dot(r, r)))]
+    z = cycle(r)
+    p, rz = z.copy(), restated_dot(r, z)
+    for k in range(maxit):
+        q = O.spmv(A, p)
+        alpha = rz / restated_dot(p, q)
+        x = alpha * p + 1.0 * x
+        r = (-alpha) * q + 1.0 * r
+        hist.append(np.sqrt(np.float64(restated_dot(r, r))))
+        if k + 1 < maxit:
+            z = cycle(r)
+            rz, rz_old = restated_dot(r, z), rz
+            p = 1.0 * z + (rz / rz_old) * p
+    return x, np.array(hist)
+
+
+@pytest.mark.parametrize("nu", PAIRS)
+def test_cycle_bits_every_degree_pair(ctx, nu):
+    """poisson3d 24 (three levels: a three-vector ring on two of them), 2 stationary cycles from a given
+    guess: the restatement's x bits, from the captured graph and from eager launches."""
+    S, b, bo, _Ho, ref, cache = problem(ctx, "poisson3d24")
+    assert S.L >= 3
+    if ("two", nu) not in cache:
+        cache[("two", nu)] = ref.solve(bo, 2, *nu)
+    xo, ho = cache[("two", nu)]
+    S.set_smoother("chebyshev", ratio=4.0)
+    S.set_sweeps(*nu)
+    try:
+        for graph in (True, False):
+            S.set_graph(graph)
+            x = S.new_vector()
+            hist = S.vcycle(x, b, 2, res_hist=True)
+            assert np.array_equal(bits(x.own_values()), bits(xo)), (nu, graph)
+            np.testing.assert_allclose(hist, ho, rtol=1e-12)
+            assert S.graph_state()["captured"] == graph
+            assert not S.graph_state()["failed"]
+    finally:
+        S.set_graph(True)
+        S.set_smoother("jacobi")
+        S.set_sweeps(1, 1)
+
+
+@pytest.mark.parametrize("nu", PAIRS)
+def test_pcg_bits_every_degree_pair(ctx, nu):
+    """2 PCG iterations: every cycle starts from a zero guess (the level-0 zero-guess rings). x and the
+    residual history are the restated iteration's bits, from pamg_pcg and from the device-resident
+    iteration (whose second half enqueues the cycle itself)."""
+    S, b, bo, Ho, ref, _cache = problem(ctx, "poisson3d24")
+    xo, ho = pcg_bits_ref(lambda r: ref.cycle(0, None, r, *nu), Ho.A[0], bo, 2)
+    S.set_smoother("chebyshev", ratio=4.0)
+    S.set_sweeps(*nu)
+    try:
+        for lookahead in (None, 0):
+            x = S.new_vector()
+            k, hist = S.pcg(x, b, 0.0, 2, lookahead=lookahead)
+            assert k == 2
+            assert np.array_equal(bits(x.own_values()), bits(xo)), (nu, lookahead)
+            assert np.array_equal(bits(hist), bits(ho)), (nu, lookahead)
+    finally:
+        S.set_smoother("jacobi")
+        S.set_sweeps(1, 1)
+
+
+def test_spare_vector_history(ctx):
+    """poisson3d 64 runs the cross-cycle pipeline: after 3 Jacobi V(1,1) cycles the solver owns the spare
+    level-0 vector. Chebyshev V(1,3), V(3,1), V(3,3) and V(2,2) on it then give the bits of a solver on
+    the same hierarchy that never pipelined: only the degrees decide which cycles use that vector."""
+    piped, b, _bo, _Ho, _ref, cache = problem(ctx, "poisson3d64")
+    assert piped.bench_chain(piped.new_vector(), b, 1) is not None  # (this hierarchy does pipeline)
+    piped.vcycle(piped.new_vector(), b, 3)
+    fresh = AMGSolver(ctx, cache["hierarchy"])
+    try:
+        for nu in ((1, 3), (3, 1), (3, 3), (2, 2)):
+            got = []
+            for S in (piped, fresh):
+                S.set_smoother("chebyshev", ratio=4.0)
+                S.set_sweeps(*nu)
+                x = S.new_vector()
+                S.vcycle(x, b, 2)
+                got.append(bits(x.own_values()))
+            assert np.array_equal(got[0], got[1]), nu
+    finally:
+        piped.set_smoother("jacobi")
+        piped.set_sweeps(1, 1)
 
 
 def test_residuals_match_the_recorded_convergence(ctx):

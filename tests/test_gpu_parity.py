@@ -431,6 +431,43 @@ def test_vcycle_sweeps_bit_exact(ctx, nu1, nu2):
         S.set_sweeps(0, 1)
 
 
+_sweeps_problem = {}
+
+
+@pytest.mark.parametrize("nu1", [1, 2, 3, 4])
+@pytest.mark.parametrize("nu2", [1, 2, 3, 4])
+def test_vcycle_every_sweep_pair_bit_exact(ctx, nu1, nu2):
+    """Every V(nu1, nu2) with 1 <= nu1, nu2 <= 4 on poisson3d 16 (three levels), 2 cycles from a given
+    guess, graph and eager, against the oracle's set_sweeps: both parities of the pre- and the
+    post-smoothing ping-pong, V(1, nu2) with the fused level-0 pass, V(1, 1) through the pipeline."""
+    if not _sweeps_problem:
+        kind, n, mc = "poisson3d", 16, 100
+        be = pa.SequentialBackend(1)
+        A, offs, xs = pa.generate_problem(be, kind, n)
+        S = AMGSolver(ctx, pa.build_hierarchy(be, A, offs, pa.SAParams(max_coarse=mc)))
+        b = PVector(ctx, S.A[0].nrows)
+        mul(b, S.A[0], PVector(ctx, S.A[0].nrows, 0, xs[0]))
+        Ao = O.generate(kind, n, n, n)
+        Ho = O.setup(Ao, max_coarse=mc)
+        assert Ho.nlevels == S.L >= 3
+        _sweeps_problem.update(S=S, b=b, bo=O.spmv(Ao, O.xstar(Ao.nrows)), Ho=Ho)
+    S, b, bo, Ho = (_sweeps_problem[k] for k in ("S", "b", "bo", "Ho"))
+    Ho.set_sweeps(nu1, nu2)
+    S.set_sweeps(nu1, nu2)
+    try:
+        xo, ho = Ho.solve(bo, 2, res_hist=True)
+        for graph in (True, False):
+            S.set_graph(graph)
+            x = S.new_vector()
+            hist = S.vcycle(x, b, 2, res_hist=True)
+            assert np.array_equal(bits(x.own_values()), bits(xo)), (nu1, nu2, graph)
+            np.testing.assert_allclose(hist, ho, rtol=1e-12)
+    finally:
+        Ho.set_sweeps(1, 1)
+        S.set_sweeps(1, 1)
+        S.set_graph(True)
+
+
 def test_stream_bytes_layout(ctx, novd):
     """pamg_mat_stream_bytes: 12 B/nnz + row pointers + 16-B tile descriptors in the 32-bit
     layout; 3-B columns (+ a 4-B base per tile) in the 24-bit one; 1 B per row instead of a
