@@ -428,6 +428,54 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
  * jr_fuse, level 0 with pamg_mat_layout bit 5). */
 int pamg_hier_bench_chain(pamg_hier* H, pamg_vec* x, const pamg_vec* b, int reps, double* avg_ms);
 
+/* ---- several right-hand sides (SPEC §S13; one part only) ----
+ * A multi-vector (the specification's pamg_mvec) is a pamg_vec handle with ncols columns, 1 <= ncols
+ * <= 8, each of n_own + n_ghost doubles, column-major in one allocation: column c starts `stride`
+ * doubles after column c - 1, stride = n_own + n_ghost rounded up to a multiple of 32, so every column
+ * starts 256-byte aligned like a vector of its own. A vector of pamg_vec_create is a multi-vector of one
+ * column; the single-column entry points see column 0 of a multi-vector. Host arrays are column-major with
+ * leading dimension n_own. pamg_mvec_column returns a non-owning pamg_vec that aliases column c: the whole
+ * single-column API works on it, destroying it frees nothing, and the multi-vector must outlive it.
+ * PAMG_E_ARG for ncols outside 1..8 or a column outside 0..ncols-1. */
+int pamg_mvec_create(pamg_ctx* ctx, int64_t n_own, int64_t n_ghost, int ncols, pamg_vec** out);
+int pamg_mvec_destroy(pamg_vec* mv);
+int pamg_mvec_size(const pamg_vec* mv, int64_t* n_own, int64_t* n_ghost, int* ncols, int64_t* stride);
+int pamg_mvec_upload(pamg_ctx* ctx, pamg_vec* mv, const double* own /* n_own x ncols */);
+int pamg_mvec_download(pamg_ctx* ctx, const pamg_vec* mv, double* own /* n_own x ncols */);
+int pamg_mvec_column(pamg_vec* mv, int c, pamg_vec** view);
+/* A multi-column operation on columns 0 .. k-1 is k independent single-column operations: column c of
+ * every result carries the bits of the single-column call on column c, nothing is summed across columns,
+ * and a NaN in one column never reaches another. Where the operator is in the block-row layout
+ * (pamg_mat_layout bit 15) one launch of k_rows_bsr_mc serves up to four columns — the matrix is
+ * streamed once for them —, everywhere else the columns run one after the other through the single-column
+ * kernels. PAMG_E_ARG where the column counts or shapes disagree or X is B or Y; PAMG_E_STATE on a
+ * context of several parts; a refused call launches nothing.
+ * pamg_spmm: Y = A X. pamg_residual_multi: R = B - A X, nrm2[c] = ||R_c|| (k values, may be NULL). */
+int pamg_spmm(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* X, pamg_vec* Y);
+int pamg_residual_multi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* X, const pamg_vec* B, pamg_vec* R,
+                        double* nrm2 /* k, may be NULL */);
+/* ncycles V-cycles on every column of X (pamg_vcycle's bits per column; res_hist[j * k + c] = column c's
+ * residual norm after cycle j, one host wait per cycle). The cycle is the plan of pamg_vcycle without the
+ * temporally blocked passes and the cross-cycle pipeline (same bits), captured and replayed as one graph
+ * keyed on (X, B, k). Also PAMG_E_STATE on a hierarchy with a level-0 permutation (pamg_hier_set_perm).
+ * The hierarchy keeps k-column copies of its work vectors from the first multi-column call on;
+ * pamg_hier_profile ignores these calls. */
+int pamg_vcycle_multi(pamg_ctx* ctx, pamg_hier* H, pamg_vec* X, const pamg_vec* B, int ncycles,
+                      double* res_hist /* ncycles x k, may be NULL */);
+/* pamg_pcg on every column (SPEC §S13): each column has its own rho, alpha, beta, ||r_0|| and stopping
+ * test, and stops when it converges, when ||r_0|| = 0, or at maxit; from then on its x is not written
+ * again, and the call ends when every column has stopped. iters[c] and res_hist[c * (maxit + 1) + j], j <=
+ * iters[c], are pamg_pcg's for column c alone, bit for bit. The dots of one step are enqueued together
+ * and the host waits once per step, not once per column. */
+int pamg_pcg_multi(pamg_ctx* ctx, pamg_hier* H, pamg_vec* X, const pamg_vec* B, double rtol, int maxit,
+                   int* iters /* k */, double* res_hist /* k x (maxit+1), may be NULL */);
+/* pamg_bench_rowop on k columns: ops 0, 1, 2, 3 and 6 as there (op 6's x_{k-1} a zeroed multi-vector of
+ * the call's); op 7 is one point-block Jacobi sweep and op 8 one point-block Chebyshev step k >= 1 (SPEC
+ * §S12; the matrix carries block data, else PAMG_E_STATE), `omega` serving as c2 (and c1) and x_{k-1}
+ * zeroed; the result stays in Y. */
+int pamg_bench_rowop_multi(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* X, const pamg_vec* B,
+                           pamg_vec* Y, double omega, int reps, double* avg_ms);
+
 /* Process-wide knobs. Applied to later pamg_mat_upload calls: "tile_nnz" (1024 | 2048 | 4096,
  * nonzero budget of a 256-row tile), "tile_order" (0 natural | 1 banded XCD-blocked), "col24",
  * "long_tiles", "row_len8", "value_dict" (0 | 1 | 2), "col_dict", "col_dict_anchor", "col_dict_tile", "x_stage", "tm_tile_dicts" (0 | 1

@@ -25,7 +25,7 @@ using SparseArrays
 export Context, ExchangePlan, DeviceVector, DeviceMatrix, HostCSR, VCycle, ExchangeTask, PamgError,
        download_own, download_ghosts, exchange_begin, residual!, jacobi!, jacobi_residual!, chebyshev!, chebyshev_coeffs, vcycle!, pcg!, set_sweeps!, set_smoother!,
        fill_xstar!, estimate_lmax, set_omega!, block_diag, set_block_diag!, block_size, block_jacobi!, block_chebyshev!,
-       estimate_lmax_block,
+       estimate_lmax_block, DeviceMultiVector, column, spmm!, mvec_size,
        set_perm!, setup_hierarchy, gen_grid, gen_xstar, read_mtx, rcm_order, locality_order, unique_id,
        comm_init!, runtime_versions, hip, World, world_spmv!, world_exchange!, world_dot, world_vcycle!,
        world_pcg!, world_abort!, world_reset!, world_broken, set_tag!
@@ -988,6 +988,100 @@ function bench_chain(x::DeviceVector, M::VCycle, b::DeviceVector; reps::Integer 
     ms = Ref{Cdouble}(0.0)
     check(ccall((:pamg_hier_bench_chain, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}),
                 M.h, x.h, b.h, reps, ms))
+    ms[]
+end
+
+# ------------------------------------------------------------------ several right-hand sides (SPEC §S13)
+"""
+    DeviceMultiVector(ctx, n_own, ncols[, n_ghost])
+    DeviceMultiVector(ctx, values::AbstractMatrix[, n_ghost])
+
+`ncols` (1..8) device vectors in one allocation, column-major, every column 256-byte aligned
+(`pamg_mvec_create`). One part only. `column(X, c)` (1-based) is a `DeviceVector` aliasing column c: it owns
+nothing, and X must outlive it.
+"""
+mutable struct DeviceMultiVector
+    h::Ptr{Cvoid}
+    ctx::Context
+    n_own::Int
+    n_ghost::Int
+    ncols::Int
+end
+function DeviceMultiVector(ctx::Context, n_own::Integer, ncols::Integer, n_ghost::Integer = 0)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pamg_mvec_create, libpamg), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                ctx.h, n_own, n_ghost, ncols, h))
+    X = DeviceMultiVector(h[], ctx, n_own, n_ghost, ncols)
+    finalizer(close, X)
+end
+function DeviceMultiVector(ctx::Context, values::AbstractMatrix{<:Real}, n_ghost::Integer = 0)
+    X = DeviceMultiVector(ctx, size(values, 1), size(values, 2), n_ghost)
+    own = Matrix{Float64}(values)
+    check(ccall((:pamg_mvec_upload, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), ctx.h, X.h, own))
+    X
+end
+function Base.close(X::DeviceMultiVector)
+    X.h == C_NULL && return nothing
+    ccall((:pamg_mvec_destroy, libpamg), Cint, (Ptr{Cvoid},), X.h)
+    X.h = C_NULL
+    nothing
+end
+"(n_own, n_ghost, ncols, column stride in doubles) as the library holds them."
+function mvec_size(X::DeviceMultiVector)
+    o, g, k, s = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0), Ref{Int64}(0)
+    check(ccall((:pamg_mvec_size, libpamg), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Cint}, Ptr{Int64}),
+                X.h, o, g, k, s))
+    (Int(o[]), Int(g[]), Int(k[]), Int(s[]))
+end
+"The own values as an n_own x ncols Matrix."
+function download_own(X::DeviceMultiVector)
+    out = Matrix{Float64}(undef, X.n_own, X.ncols)
+    check(ccall((:pamg_mvec_download, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), X.ctx.h, X.h, out))
+    out
+end
+"Column c (1-based) as a DeviceVector that aliases it."
+function column(X::DeviceMultiVector, c::Integer)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pamg_mvec_column, libpamg), Cint, (Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}), X.h, c - 1, h))
+    v = DeviceVector(h[], X.ctx, X.n_own, X.n_ghost)
+    finalizer(close, v)
+end
+"Y = A X, each column with `mul!`'s bits."
+spmm!(Y::DeviceMultiVector, A::DeviceMatrix, X::DeviceMultiVector) =
+    (check(ccall((:pamg_spmm, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                 A.ctx.h, A.h, X.h, Y.h)); Y)
+"R = B - A X; with `norm = true` returns the ncols norms instead of R."
+function residual!(R::DeviceMultiVector, A::DeviceMatrix, X::DeviceMultiVector, B::DeviceMultiVector; norm::Bool = false)
+    nr = zeros(X.ncols)
+    check(ccall((:pamg_residual_multi, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}),
+                A.ctx.h, A.h, X.h, B.h, R.h, norm ? pointer(nr) : Ptr{Cdouble}(C_NULL)))
+    norm ? nr : R
+end
+"`ncycles` V-cycles on every column; with `res_hist = true` returns the k x ncycles residual norms."
+function vcycle!(X::DeviceMultiVector, M::VCycle, B::DeviceMultiVector; ncycles::Integer = 1, res_hist::Bool = false)
+    hist = zeros(X.ncols, ncycles)
+    check(ccall((:pamg_vcycle_multi, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cdouble}),
+                M.ctx.h, M.h, X.h, B.h, ncycles, res_hist ? pointer(hist) : Ptr{Cdouble}(C_NULL)))
+    res_hist ? hist : X
+end
+"CG per column (SPEC §S13): returns (iteration counts, residual histories), each column's those of `pcg!` on it alone."
+function pcg!(X::DeviceMultiVector, M::VCycle, B::DeviceMultiVector; rtol::Real = 1e-8, maxit::Integer = 100)
+    hist = zeros(maxit + 1, X.ncols)
+    it = zeros(Cint, X.ncols)
+    check(ccall((:pamg_pcg_multi, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cint}, Ptr{Cdouble}),
+                M.ctx.h, M.h, X.h, B.h, rtol, maxit, it, hist))
+    (Int.(it), [hist[1:it[c]+1, c] for c in 1:X.ncols])
+end
+"`bench_rowop` on every column of X (ops 0-3, 6; 7 / 8: the point-block Jacobi sweep / Chebyshev step)."
+function bench_rowop(A::DeviceMatrix, op::Integer, X::DeviceMultiVector, B::Union{Nothing,DeviceMultiVector},
+                     Y::DeviceMultiVector; omega::Real = 0.0, reps::Integer = 20)
+    ms = Ref{Cdouble}(0.0)
+    check(ccall((:pamg_bench_rowop_multi, libpamg), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cint, Ptr{Cdouble}),
+                A.ctx.h, A.h, op, X.h, B === nothing ? C_NULL : B.h, Y.h, omega, reps, ms))
     ms[]
 end
 

@@ -116,6 +116,17 @@ SIGNATURES = {
     "pamg_hier_profile_read": [vp, vp],
     "pamg_bench_rowop": [vp, vp, i32, vp, vp, vp, dbl, i32, pdbl],
     "pamg_hier_bench_chain": [vp, vp, vp, i32, pdbl],
+    "pamg_mvec_create": [vp, i64, i64, i32, pvp],
+    "pamg_mvec_destroy": [vp],
+    "pamg_mvec_size": [vp, pi64, pi64, C.POINTER(C.c_int), pi64],
+    "pamg_mvec_upload": [vp, vp, vp],
+    "pamg_mvec_download": [vp, vp, vp],
+    "pamg_mvec_column": [vp, i32, pvp],
+    "pamg_spmm": [vp, vp, vp, vp],
+    "pamg_residual_multi": [vp, vp, vp, vp, vp, vp],
+    "pamg_vcycle_multi": [vp, vp, vp, vp, i32, vp],
+    "pamg_pcg_multi": [vp, vp, vp, vp, dbl, i32, vp, vp],
+    "pamg_bench_rowop_multi": [vp, vp, i32, vp, vp, vp, dbl, i32, pdbl],
     "pamg_set_option": [C.c_char_p, i64],
     "pamg_get_option": [C.c_char_p, pi64],
     "pamg_hcsr_create": [i64, i64, i64, pvp],

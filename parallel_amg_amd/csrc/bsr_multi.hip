@@ -1,0 +1,183 @@
+// bsr_multi.hip — the block-row kernel on several right-hand sides (SPEC §S13; gfx950).
+//
+// k_rows_bsr (kernels.hip) streams 8 + 4 / bs^2 bytes of matrix per stored nonzero and 2 to 7 % as many
+// bytes of vectors, so a second right-hand side costs the whole stream again. k_rows_bsr_mc walks the same
+// slices with the same lanes and loads each block slot — its column and its BS^2 values — once for NV
+// columns: per column the lane loads the block's BS entries of x and adds s[c][d] = s[c][d] + v_de x_ce
+// in e order, each product and each add rounded once (-ffp-contract=off), which is k_rows_bsr's sum for
+// that column alone. Nothing is summed across columns, and a padded slot is skipped whole. The epilogues
+// are epilogue<OP>'s and the fused block sweeps k_rows_bsr's, per column, with the diagonal entries and
+// the lane's d_binv block loaded once. No LDS, no barrier.
+// A unit of its own: kernels.hip's code object stays as it is ("Several right-hand sides").
+
+#include "multi_cols.h"
+#include "pamg_device.h"
+
+namespace pamg {
+namespace {
+
+#include "row_epilogue.h"
+
+// The columns of one launch, by value in the kernel's arguments: any subset of a multi-vector's columns
+template <int NV>
+struct McIn {
+    const double* p[NV];
+};
+template <int NV>
+struct McOut {
+    double* p[NV];
+};
+
+template <int BS, int OP, int FUSE, int NV>
+__global__ __launch_bounds__(kBlock) void k_rows_bsr_mc(int nb, int ns, const int64_t* __restrict__ soff,
+                                                        const int* __restrict__ bcol, const double* __restrict__ val,
+                                                        const double* __restrict__ diag,
+                                                        const double* __restrict__ binv, int x16, McIn<NV> x,
+                                                        McIn<NV> b, McOut<NV> y, double omega, double c1,
+                                                        McIn<NV> xold) {
+    const int lane = threadIdx.x & (kEllW - 1);
+    const int sl = blockIdx.x * kBsrSlices + (threadIdx.x >> 6);
+    if (sl >= ns) return;
+    const int64_t k0 = soff[sl], k1 = soff[sl + 1];
+    const int m = sl * kEllW + lane;
+    double s[NV][BS];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+#pragma unroll
+        for (int d = 0; d < BS; ++d) s[c][d] = 0.0;
+    }
+    const int* cp = bcol + k0 * kEllW + lane;
+    const double* vp = val + k0 * (BS * BS) * kEllW + lane;
+    for (int64_t k = k0; k < k1; ++k, cp += kEllW, vp += BS * BS * kEllW) {
+        const int col = *cp;
+        if (col < 0) continue;
+        double v[BS * BS];
+#pragma unroll
+        for (int j = 0; j < BS * BS; ++j) v[j] = vp[j * kEllW];
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            double xe[BS];
+            bsr_load_x<BS>(x.p[c], col, x16 != 0, xe);
+#pragma unroll
+            for (int d = 0; d < BS; ++d) {
+#pragma unroll
+                for (int e = 0; e < BS; ++e) {
+                    const double p = v[d * BS + e] * xe[e];
+                    s[c][d] = s[c][d] + p;
+                }
+            }
+        }
+    }
+    if (m >= nb) return;
+    const int64_t r0 = (int64_t)m * BS;
+    if constexpr (FUSE == 0) {
+#pragma unroll
+        for (int d = 0; d < BS; ++d) {
+            double dg = 1.0;
+            if constexpr (kDiagOp<OP>) dg = diag[r0 + d];
+#pragma unroll
+            for (int c = 0; c < NV; ++c)
+                epilogue<OP>((int)(r0 + d), s[c][d], x.p[c], b.p[c], y.p[c], omega, dg, c1, xold.p[c]);
+        }
+    } else {
+        double di[BS * BS];
+#pragma unroll
+        for (int j = 0; j < BS * BS; ++j) di[j] = binv[r0 * BS + j];
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            const double* __restrict__ xc = x.p[c];
+            const double* __restrict__ bc = b.p[c];
+            const double* __restrict__ xo = xold.p[c];
+            double* __restrict__ yc = y.p[c];
+            double u[BS];
+#pragma unroll
+            for (int d = 0; d < BS; ++d) u[d] = bc[r0 + d] - s[c][d];
+#pragma unroll
+            for (int d = 0; d < BS; ++d) {
+                double w = 0.0;
+#pragma unroll
+                for (int j = 0; j < BS; ++j) {
+                    const double p = di[d * BS + j] * u[j];
+                    w = w + p;
+                }
+                const int64_t r = r0 + d;
+                if constexpr (FUSE == 1) {
+                    const double vv = omega * w;
+                    yc[r] = xc[r] + vv;
+                } else {
+                    const double xi = xc[r];
+                    const double vv = omega * w;
+                    const double e = xi - (xo ? xo[r] : 0.0);
+                    const double q = c1 * e;
+                    const double t = q + vv;
+                    yc[r] = xi + t;
+                }
+            }
+        }
+    }
+}
+
+template <int OP, int FUSE, int NV>
+void launch_chunk(const pamg_mat& A, const double* const* x, const double* const* b, const double* const* xold,
+                  double* const* y, double omega, double c1, hipStream_t s) {
+    const BsrSet& B = A.bsr;
+    McIn<NV> xa, ba, oa;
+    McOut<NV> ya;
+    int x16 = 1;  // the 16-byte x loads only where every column of the launch allows them
+    for (int c = 0; c < NV; ++c) {
+        xa.p[c] = x[c];
+        ba.p[c] = b ? b[c] : nullptr;
+        oa.p[c] = xold ? xold[c] : nullptr;
+        ya.p[c] = y[c];
+        if ((reinterpret_cast<uintptr_t>(x[c]) & 15) != 0) x16 = 0;
+    }
+    auto go = [&](auto kern) {
+        kern<<<B.grid, kBlock, 0, s>>>((int)B.nb, (int)B.nslices, B.d_soff, B.d_bcol, B.d_val, A.d_diag, A.d_binv, x16,
+                                       xa, ba, ya, omega, c1, oa);
+    };
+    switch (B.bs) {
+        case 2: go(k_rows_bsr_mc<2, OP, FUSE, NV>); break;
+        case 3: go(k_rows_bsr_mc<3, OP, FUSE, NV>); break;
+        default: go(k_rows_bsr_mc<4, OP, FUSE, NV>); break;
+    }
+}
+
+template <int NV>
+void launch_chunk_op(const pamg_mat& A, int op, int fuse, const double* const* x, const double* const* b,
+                     const double* const* xold, double* const* y, double omega, double c1, hipStream_t s) {
+    if (fuse == 1) return launch_chunk<OP_RESID, 1, NV>(A, x, b, nullptr, y, omega, 0.0, s);
+    if (fuse == 2) return launch_chunk<OP_RESID, 2, NV>(A, x, b, xold, y, omega, c1, s);
+    switch (op) {
+        case OP_SPMV: launch_chunk<OP_SPMV, 0, NV>(A, x, b, nullptr, y, omega, 0.0, s); break;
+        case OP_RESID: launch_chunk<OP_RESID, 0, NV>(A, x, b, nullptr, y, omega, 0.0, s); break;
+        case OP_JACOBI: launch_chunk<OP_JACOBI, 0, NV>(A, x, b, nullptr, y, omega, 0.0, s); break;
+        case OP_CHEB: launch_chunk<OP_CHEB, 0, NV>(A, x, b, xold, y, omega, c1, s); break;
+        default: launch_chunk<OP_PROLONG, 0, NV>(A, x, b, nullptr, y, omega, 0.0, s); break;
+    }
+}
+
+}  // namespace
+
+void launch_bsr_multi(const pamg_mat& A, int op, int fuse, int ncols, const double* const* x, const double* const* b,
+                      const double* const* xold, double* const* y, double omega, double c1, hipStream_t s) {
+    if (A.bsr.nb <= 0) return;
+    int first[mc::kMaxCols], width[mc::kMaxCols];
+    const int n = mc::chunks(ncols, first, width);
+    for (int i = 0; i < n; ++i) {
+        const int c = first[i];
+        const double* const* bc = b ? b + c : nullptr;
+        const double* const* oc = xold ? xold + c : nullptr;
+        if (width[i] == 4) {
+            launch_chunk_op<4>(A, op, fuse, x + c, bc, oc, y + c, omega, c1, s);
+        } else if (width[i] == 2) {
+            launch_chunk_op<2>(A, op, fuse, x + c, bc, oc, y + c, omega, c1, s);
+        } else if (fuse) {  // one column: today's launchers
+            launch_bsr_block(A, fuse == 1 ? BM_JACOBI : BM_CHEB, x[c], b[c], oc ? oc[0] : nullptr, y[c], c1, omega, s);
+        } else {
+            const double* xo = op == OP_CHEB ? (oc ? oc[0] : nullptr) : x[c];
+            launch_rows(A, A.interior, op, x[c], bc ? bc[0] : nullptr, xo, y[c], omega, s, c1);
+        }
+    }
+}
+
+}  // namespace pamg

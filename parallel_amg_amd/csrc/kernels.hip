@@ -55,41 +55,8 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     return v;
 }
 
-// OP_JACOBI and OP_CHEB capture the row's diagonal on the way (the in-tile / in-row search).
-template <int OP>
-constexpr bool kDiagOp = OP == OP_JACOBI || OP == OP_CHEB;
-
-// The Chebyshev step k >= 1 (SPEC §S9) from the row's residual u = b_i - s: seven roundings, none
-// fused (-ffp-contract=off). xo is xold_i, +0.0 where the step follows a zero guess.
-__device__ __forceinline__ double cheb_step(double u, double xi, double xo, double d, double c1, double c2) {
-    const double v = c2 * u;
-    const double w = v / d;
-    const double e = xi - xo;
-    const double q = c1 * e;
-    const double t = q + w;
-    return xi + t;
-}
-
-template <int OP>
-__device__ __forceinline__ void epilogue(int r, double s, const double* __restrict__ x,
-                                         const double* __restrict__ b, double* __restrict__ y,
-                                         double omega, double d, double c1 = 0.0,
-                                         const double* __restrict__ xold = nullptr) {
-    if constexpr (OP == OP_SPMV) {
-        y[r] = s;
-    } else if constexpr (OP == OP_RESID) {
-        y[r] = b[r] - s;
-    } else if constexpr (OP == OP_JACOBI) {
-        const double u = b[r] - s;
-        const double v = omega * u;
-        const double w = v / d;
-        y[r] = x[r] + w;
-    } else if constexpr (OP == OP_CHEB) {
-        y[r] = cheb_step(b[r] - s, x[r], xold ? xold[r] : 0.0, d, c1, omega);
-    } else {
-        y[r] = y[r] + s;
-    }
-}
+// kDiagOp, cheb_step and epilogue<OP>: what a kernel does with a finished row sum (shared with bsr_multi.hip)
+#include "row_epilogue.h"
 
 // Sum of lp[kb..ke) left to right from +0.0 (SPEC §S3). The chain of dependent fp64 adds is
 // what bounds the long rows of the coarse operators, so nothing else may sit on it: full
@@ -3212,28 +3179,7 @@ __global__ void k_pcg_dir(int64_t n, const PcgScalars* S, const double* __restri
 // BS row sums: the scalar epilogues run per d, and the fused forms (FUSE 1: block Jacobi, 2: the block
 // Chebyshev step; OP_RESID) apply D_m^-1 from the lane's BS^2 entries of d_binv in registers — k_block_update's
 // roundings in its order, with no second pass and no LDS. No barrier: a wave past the last slice leaves.
-template <int BS>
-__device__ __forceinline__ void bsr_load_x(const double* __restrict__ x, int c, bool x16, double (&xe)[BS]) {
-    const double* p = x + (int64_t)c * BS;
-    if constexpr (BS == 3) {
-        xe[0] = p[0];
-        xe[1] = p[1];
-        xe[2] = p[2];
-    } else {
-        if (x16) {
-#pragma unroll
-            for (int e = 0; e < BS; e += 2) {
-                const double2 v = *reinterpret_cast<const double2*>(p + e);
-                xe[e] = v.x;
-                xe[e + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < BS; ++e) xe[e] = p[e];
-        }
-    }
-}
-
+// (bsr_load_x, a block's BS entries of x: row_epilogue.h, shared with bsr_multi.hip)
 template <int BS, int OP, int FUSE>
 __global__ __launch_bounds__(kBlock) void k_rows_bsr(int nb, int ns, const int64_t* __restrict__ soff,
                                                      const int* __restrict__ bcol, const double* __restrict__ val,

@@ -426,6 +426,10 @@ struct pamg_ctx {
     double* d_red = nullptr;  // reduction workspace (partials + result)
     int red_cap = 0;
     double* h_red = nullptr;  // pinned host scalar
+    // the reductions of a multi-column step (SPEC §S13; allocated by the first multi-column call): column
+    // c's partials at d_redk + c * 1024, the results behind them; h_redk: the pinned results
+    double* d_redk = nullptr;
+    double* h_redk = nullptr;
     // upload staging (matrix.hip h2d): two pinned 64 MiB buffers and their DMA-done events,
     // created on first use on this context's device and owned by the context
     char* stage[2] = {nullptr, nullptr};
@@ -463,6 +467,11 @@ struct pamg_vec {
     pamg_ctx* ctx = nullptr;
     int64_t n_own = 0, n_ghost = 0;
     double* d = nullptr;  // n_own + n_ghost (+ padding)
+    // several right-hand sides (SPEC §S13; pamg_mvec_create): ncols columns of n_own + n_ghost doubles,
+    // column c at d + c * stride (pamg::mc::col_stride); the single-column entry points see column 0
+    int ncols = 1;
+    int64_t stride = 0;
+    bool owns = true;  // false: a column view (pamg_mvec_column) — d belongs to the multi-vector
 };
 
 struct pamg_mat {
@@ -561,6 +570,14 @@ inline bool bsr_fused(const pamg_mat& A) {
 }
 void launch_bsr_block(const pamg_mat& A, int mode, const double* x, const double* b, const double* xold, double* y,
                       double c1, double c2, hipStream_t s);
+// bsr_multi.hip, SPEC §S13: one row operation of a block-row operator (A.interior.bsr) on ncols columns (1 ..
+// mc::kMaxCols), column c reading x[c], b[c], xold[c] and writing y[c] with the bits of the single-column
+// launch on those four. fuse 0: the RowOp `op` (omega, c1 and xold as launch_rows takes them); fuse 1 / 2:
+// the fused block Jacobi / block Chebyshev sweep (bsr_fused(A); omega is c2). The columns are cut into
+// launches of 4, then 2 (k_rows_bsr_mc), then 1 (launch_rows / launch_bsr_block). b and xold may be null
+// where the operation reads none; an entry of xold may be null (zeros).
+void launch_bsr_multi(const pamg_mat& A, int op, int fuse, int ncols, const double* const* x, const double* const* b,
+                      const double* const* xold, double* const* y, double omega, double c1, hipStream_t s);
 // SPEC §S12 estimate step after y = A v: out[0] = v.y, out[1] = (D_b v).v (launch_lmax_step's order and
 // trees), then v <- D_b^-1 y in a pass of its own. partials holds 2 np doubles.
 void launch_lmax_step_block(const pamg_mat& A, const double* y, double* v, double* partials, int np, double* out,

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "cycle_plan.h"
+#include "multi_cols.h"
 #include "pamg_device.h"
 #include "pamg_host.h"
 
@@ -647,6 +648,22 @@ struct pamg_hier {
     std::vector<hipEvent_t> pcg_ev;
     hipGraphExec_t g_pcg[2] = {nullptr, nullptr};
     const double* gr_x = nullptr;
+    // several right-hand sides (SPEC §S13): mc_cols-column copies of the per-level work vectors and of
+    // PCG's, column c of level l's at base + c * mc_stride[l]; allocated by the first multi-column call,
+    // grown when a later call brings more columns. gm_exec: the multi-column cycle's graph, keyed on the
+    // level-0 column bases, the column count and the zero-guess flag.
+    int mc_cols = 0;
+    std::vector<int64_t> mc_stride;
+    std::vector<double*> mx, mb, mt, mr;
+    double* mu0 = nullptr;
+    double *mpcg_r = nullptr, *mpcg_z = nullptr, *mpcg_p = nullptr, *mpcg_q = nullptr;
+    hipGraphExec_t gm_exec = nullptr;
+    const double* gm_x = nullptr;
+    const double* gm_b = nullptr;
+    const double* gm_x1 = nullptr;  // (column 1 of either: the strides)
+    const double* gm_b1 = nullptr;
+    int gm_k = 0;
+    bool gm_zero0 = false;
     // level-0 locality permutation (pamg_hier_set_perm): device row i = caller row perm[i];
     // the caller's x and b are gathered into px / pb at entry and x is scattered back at exit
     int* d_perm = nullptr;
@@ -919,6 +936,8 @@ void ctx_teardown(pamg_ctx* ctx) {
     if (ctx->ev_ready) (void)hipEventDestroy(ctx->ev_ready);
     dfree(ctx->d_red);
     if (ctx->h_red) (void)hipHostFree(ctx->h_red);
+    dfree(ctx->d_redk);
+    if (ctx->h_redk) (void)hipHostFree(ctx->h_redk);
     for (int k = 0; k < 2; ++k) {
         if (ctx->stage[k]) (void)hipHostFree(ctx->stage[k]);
         if (ctx->stage_done[k]) (void)hipEventDestroy(ctx->stage_done[k]);
@@ -1268,6 +1287,7 @@ int pamg_vec_create(pamg_ctx* ctx, int64_t n_own, int64_t n_ghost, pamg_vec** ou
     ctx_ref(ctx);
     v->n_own = n_own;
     v->n_ghost = n_ghost;
+    v->stride = pamg::mc::col_stride(n_own, n_ghost);
     CHECK(dalloc(&v->d, n_own + n_ghost + kVecPad));
     HIPC(hipMemsetAsync(v->d, 0, sizeof(double) * (n_own + n_ghost + kVecPad), ctx->s_comp));
     HIPC(hipStreamSynchronize(ctx->s_comp));
@@ -1279,7 +1299,7 @@ int pamg_vec_destroy(pamg_vec* v) {
     if (!v) return PAMG_OK;
     (void)hipSetDevice(v->ctx->device);
     (void)hipStreamSynchronize(v->ctx->s_comp);
-    dfree(v->d);
+    if (v->owns) dfree(v->d);  // (a column view of a multi-vector owns nothing)
     pamg_ctx* owner = v->ctx;
     delete v;
     ctx_unref(owner);
@@ -1630,10 +1650,33 @@ static void drop_pcg_graphs(pamg_hier* H) {
     H->gr_x = nullptr;
 }
 
+// the multi-column cycle's graph (SPEC §S13)
+static void drop_multi_graph(pamg_hier* H) {
+    if (H->gm_exec) (void)hipGraphExecDestroy(H->gm_exec);
+    H->gm_exec = nullptr;
+    H->gm_x = H->gm_b = nullptr;
+    H->gm_k = 0;
+}
+
 static void drop_graph(pamg_hier* H) {
     drop_cycle_graph(H);
     drop_pipe_graphs(H);
     drop_pcg_graphs(H);
+    drop_multi_graph(H);
+}
+
+// the k-column work vectors of the multi-column calls
+static void free_multi(pamg_hier* H) {
+    for (std::vector<double*>* set : {&H->mx, &H->mb, &H->mt, &H->mr}) {
+        for (double*& p : *set) dfree(p);
+        set->clear();
+    }
+    dfree(H->mu0);
+    dfree(H->mpcg_r);
+    dfree(H->mpcg_z);
+    dfree(H->mpcg_p);
+    dfree(H->mpcg_q);
+    H->mc_cols = 0;
 }
 
 int pamg_hier_destroy(pamg_hier* H) {
@@ -1662,6 +1705,7 @@ int pamg_hier_destroy(pamg_hier* H) {
     if (H->pcg_stage) (void)hipHostFree(H->pcg_stage);
     for (auto e : H->pcg_ev) (void)hipEventDestroy(e);
     dfree(H->u0);
+    free_multi(H);
     dfree(H->d_perm);
     dfree(H->px);
     dfree(H->pb);
@@ -2584,6 +2628,518 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
             return (int)PAMG_OK;
         });
     for (double* p : scratch) dfree(p);
+    return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ several right-hand sides (SPEC §S13)
+// A multi-column operation is k independent single-column operations. One function per kind of step
+// decides how the columns run: where the operator is in the block-row layout, launch_bsr_multi streams the
+// matrix once for up to four columns; everywhere else the columns go one after the other through the
+// single-column launchers above, with the column pointers offset. One part only.
+
+namespace {
+
+using pamg::mc::kMaxCols;
+
+// The columns of one operand of a multi-column step (any subset of a multi-vector's columns)
+struct Cols {
+    double* p[kMaxCols] = {};
+};
+
+Cols cols_of(double* base, int64_t stride, int k) {
+    Cols c;
+    for (int j = 0; j < k; ++j) c.p[j] = base + (int64_t)j * stride;
+    return c;
+}
+Cols cols_of(const pamg_vec* v) { return cols_of(v->d, v->stride, v->ncols); }
+
+// columns at[0 .. m - 1] of c
+Cols subset(const Cols& c, const int* at, int m) {
+    Cols out;
+    for (int j = 0; j < m; ++j) out.p[j] = c.p[at[j]];
+    return out;
+}
+
+// y_c = op(A, x_c[, b_c]) for k columns: apply's bits per column
+int apply_multi(pamg_ctx* ctx, const pamg_mat* A, int op, int k, const Cols& x, const Cols* b, const Cols& y,
+                double omega, double c1 = 0.0, const Cols* xold = nullptr) {
+    if (k > 1 && A->interior.bsr) {
+        // (a block-row operator has no ghost column: nothing to exchange)
+        if (op == pamg::OP_CHEB && !A->d_diag && A->nrows > 0)
+            return fail(PAMG_E_ARG, "chebyshev: a square operator with a nonzero diagonal is needed");
+        pamg::launch_bsr_multi(*A, op, 0, k, x.p, b ? b->p : nullptr, xold ? xold->p : nullptr, y.p, omega, c1,
+                               ctx->s_comp);
+        HIPC(hipGetLastError());
+        return PAMG_OK;
+    }
+    for (int c = 0; c < k; ++c)
+        CHECK(apply(ctx, A, op, x.p[c], b ? b->p[c] : nullptr, y.p[c], omega, c1, xold ? xold->p[c] : nullptr));
+    return PAMG_OK;
+}
+
+// smooth_step on k columns (in and xold null where the step names none)
+int smooth_step_multi(pamg_ctx* ctx, const pamg_mat* A, bool blk, plan::Op op, int k, const Cols* in, const Cols& b,
+                      const Cols* xold, const Cols& out, double c1, double c2) {
+    hipStream_t s = ctx->s_comp;
+    if (!(k > 1 && A->interior.bsr)) {
+        for (int c = 0; c < k; ++c)
+            CHECK(smooth_step(ctx, A, blk, op, in ? in->p[c] : nullptr, b.p[c], xold ? xold->p[c] : nullptr, out.p[c], c1,
+                              c2));
+        return PAMG_OK;
+    }
+    if (blk) {  // block_step's three forms
+        const int mode = op == plan::CHEB ? pamg::BM_CHEB : op == plan::SMOOTH ? pamg::BM_JACOBI : pamg::BM_ZERO;
+        if (mode == pamg::BM_ZERO) {
+            for (int c = 0; c < k; ++c) pamg::launch_block_update(*A, mode, b.p[c], nullptr, nullptr, out.p[c], 0.0, c2, s);
+        } else if (pamg::bsr_fused(*A)) {
+            pamg::launch_bsr_multi(*A, pamg::OP_RESID, mode == pamg::BM_JACOBI ? 1 : 2, k, in->p, b.p,
+                                   xold ? xold->p : nullptr, out.p, c2, c1, s);
+        } else {
+            CHECK(apply_multi(ctx, A, pamg::OP_RESID, k, *in, &b, out, 0.0));
+            for (int c = 0; c < k; ++c)
+                pamg::launch_block_update(*A, mode, out.p[c], in->p[c], xold ? xold->p[c] : nullptr, out.p[c], c1, c2, s);
+        }
+        HIPC(hipGetLastError());
+        return PAMG_OK;
+    }
+    if (op == plan::CHEB) return apply_multi(ctx, A, pamg::OP_CHEB, k, *in, &b, out, c2, c1, xold);
+    if (op == plan::SMOOTH) return apply_multi(ctx, A, pamg::OP_JACOBI, k, *in, &b, out, c2);
+    for (int c = 0; c < k; ++c) pamg::launch_jacobi_zero(A->nrows, b.p[c], A->d_diag, c2, out.p[c], s);
+    HIPC(hipGetLastError());
+    return PAMG_OK;
+}
+
+// ghost capacity of level l's vectors (pamg_hier_create's rule)
+int64_t level_ghosts(const pamg_hier* H, int l) {
+    int64_t g = 0;
+    if (H->A[l]->plan) g = std::max(g, H->A[l]->plan->n_ghost);
+    if (l < H->L - 1 && H->R[l]->plan) g = std::max(g, H->R[l]->plan->n_ghost);
+    if (l > 0 && H->P[l - 1]->plan) g = std::max(g, H->P[l - 1]->plan->n_ghost);
+    return g;
+}
+
+int alloc_cols(pamg_ctx* ctx, double** p, int k, int64_t stride) {
+    const int64_t n = (int64_t)k * stride + kVecPad;
+    CHECK(dalloc(p, n));
+    return dzero(ctx, *p, sizeof(double) * (size_t)n);
+}
+
+// The hierarchy's work vectors in k columns: allocated on the first multi-column call, grown (and the
+// cycle's graph dropped) when a later call brings more columns.
+int ensure_multi(pamg_hier* H, int k) {
+    if (k <= H->mc_cols) return PAMG_OK;
+    pamg_ctx* ctx = H->ctx;
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    drop_multi_graph(H);
+    free_multi(H);
+    const int L = H->L;
+    H->mc_stride.assign(L, 0);
+    for (std::vector<double*>* set : {&H->mx, &H->mb, &H->mt, &H->mr}) set->assign(L, nullptr);
+    for (int l = 0; l < L; ++l) {
+        H->mc_stride[l] = pamg::mc::col_stride(H->nown[l], level_ghosts(H, l));
+        if (l > 0) {
+            CHECK(alloc_cols(ctx, &H->mx[l], k, H->mc_stride[l]));
+            CHECK(alloc_cols(ctx, &H->mb[l], k, H->mc_stride[l]));
+        }
+        if (l < L - 1) {
+            CHECK(alloc_cols(ctx, &H->mt[l], k, H->mc_stride[l]));
+            CHECK(alloc_cols(ctx, &H->mr[l], k, H->mc_stride[l]));
+        }
+    }
+    H->mc_cols = k;
+    return PAMG_OK;
+}
+
+// the multi-column cycle's plan: pamg_vcycle's without the temporally blocked level-0 pass (same bits)
+plan::CycleSpec cycle_spec_multi(const pamg_hier* H, bool zero0) {
+    plan::CycleSpec sp = cycle_spec(H, zero0);
+    sp.l0_fused = false;
+    return sp;
+}
+
+// vcycle_enqueue on k columns: the same plan::plan_cycle step list, the roles resolved per column.
+// Not profiled (pamg_hier_profile ignores multi-column calls).
+int vcycle_enqueue_multi(pamg_hier* H, int k, const Cols& x, const Cols& b, bool zero0) {
+    pamg_ctx* ctx = H->ctx;
+    hipStream_t s = ctx->s_comp;
+    const int L = H->L;
+    if (L == 1) {
+        for (int c = 0; c < k; ++c) CHECK(coarse_solve(H, b.p[c], x.p[c], s));
+        HIPC(hipGetLastError());
+        return PAMG_OK;
+    }
+    const plan::CyclePlan cp = plan::plan_cycle(cycle_spec_multi(H, zero0));
+    if (cp.needs_u0 && !H->mu0) return fail(PAMG_E_STATE, "vcycle_multi: the cycle lacks its spare level-0 vector");
+    auto vec = [&](int l, plan::Role r) -> Cols {
+        if (l == 0 && r == plan::X) return x;
+        if (l == 0 && r == plan::B) return b;
+        double* const v[5] = {H->mx[l], H->mb[l], H->mt[l], H->mr[l], H->mu0};
+        return cols_of(v[r], H->mc_stride[l], k);
+    };
+    for (const plan::Step& st : cp.steps) {
+        const int l = st.level;
+        const Cols bl = vec(l, plan::B);
+        Cols in, xo;
+        if (st.in != plan::NONE) in = vec(st.op == plan::PROLONG ? l + 1 : l, st.in);
+        if (st.xold != plan::NONE) xo = vec(l, st.xold);
+        const Cols out = vec(l, st.out);
+        switch (st.op) {
+            case plan::RESID:
+                CHECK(apply_multi(ctx, H->A[l], pamg::OP_RESID, k, in, &bl, out, 0.0));
+                break;
+            case plan::JACOBI_RESID:
+                return fail(PAMG_E_STATE, "vcycle_multi: the plan names a temporally blocked pass");
+            case plan::RESTRICT:
+                CHECK(apply_multi(ctx, H->R[l], pamg::OP_SPMV, k, in, nullptr, vec(l + 1, plan::B), 0.0));
+                break;
+            case plan::COARSE:
+                for (int c = 0; c < k; ++c) CHECK(coarse_solve(H, in.p[c], out.p[c], s));
+                break;
+            case plan::PROLONG:
+                CHECK(apply_multi(ctx, H->P[l], pamg::OP_PROLONG, k, in, nullptr, out, 0.0));
+                break;
+            default: {
+                double c1, c2;
+                smooth_coeffs(H, l, st.k, &c1, &c2);
+                CHECK(smooth_step_multi(ctx, H->A[l], block_level(H, l), st.op, k, st.in == plan::NONE ? nullptr : &in, bl,
+                                        st.xold == plan::NONE ? nullptr : &xo, out, c1, c2));
+            }
+        }
+    }
+    HIPC(hipGetLastError());
+    return PAMG_OK;
+}
+
+// ncycles multi-column cycles on the columns x / b (stride sx / sb apart): graph replay when enabled, one
+// exec keyed on the two bases, their strides, the column count and the zero-guess flag.
+int vcycle_multi_raw(pamg_hier* H, int k, double* x, int64_t sx, double* b, int64_t sb, int ncycles, bool zero0) {
+    pamg_ctx* ctx = H->ctx;
+    CHECK(ensure_multi(H, k));
+    if (H->L > 1 && !H->mu0 && plan::plan_cycle(cycle_spec_multi(H, zero0)).needs_u0)
+        CHECK(alloc_cols(ctx, &H->mu0, H->mc_cols, H->mc_stride[0]));
+    const Cols xc = cols_of(x, sx, k), bc = cols_of(b, sb, k);
+    // (the strides ride in the key as the distance of column 1: the bases alone do not tell two layouts apart)
+    const double* kx = x + sx;
+    const double* kb = b + sb;
+    if (H->use_graph && (!H->gm_exec || H->gm_x != x || H->gm_b != b || H->gm_k != k || H->gm_zero0 != zero0 ||
+                         H->gm_x1 != kx || H->gm_b1 != kb)) {
+        drop_multi_graph(H);
+        if (capture_graph(ctx->s_comp, [&] { return vcycle_enqueue_multi(H, k, xc, bc, zero0); }, &H->gm_exec)) {
+            H->gm_x = x;
+            H->gm_b = b;
+            H->gm_x1 = kx;
+            H->gm_b1 = kb;
+            H->gm_k = k;
+            H->gm_zero0 = zero0;
+        } else {
+            H->gm_exec = nullptr;
+            capture_failed(H, "multi-column V-cycle");
+        }
+    }
+    if (H->use_graph && H->gm_exec) {
+        for (int j = 0; j < ncycles; ++j) HIPC(hipGraphLaunch(H->gm_exec, ctx->s_comp));
+    } else {
+        for (int j = 0; j < ncycles; ++j) CHECK(vcycle_enqueue_multi(H, k, xc, bc, zero0 && j == 0));
+    }
+    return PAMG_OK;
+}
+
+// The k-wide reduction workspace beside ctx->d_red
+int ensure_redk(pamg_ctx* ctx) {
+    if (ctx->d_redk) return PAMG_OK;
+    HIPC(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_redk), kMaxCols * sizeof(double)));
+    return dalloc(&ctx->d_redk, (int64_t)kMaxCols * 1024 + kMaxCols);
+}
+
+// m deterministic sums of one step: enqueue(j, np, partials, result, stream) puts sum j's partial and
+// final kernels on the compute stream (launch_dot's grid and trees, its own partials), then the host
+// waits once for all of them.
+template <class F>
+int reduce_multi(pamg_ctx* ctx, int64_t n, int m, double* out, F enqueue) {
+    hipStream_t s = ctx->s_comp;
+    const int np = pamg::dot_partials(n);
+    if (np > 1024 || m > kMaxCols) return fail(PAMG_E_STATE, "reduction workspace too small");
+    if (m <= 0) return PAMG_OK;
+    CHECK(ensure_redk(ctx));
+    double* res = ctx->d_redk + (int64_t)kMaxCols * 1024;
+    for (int j = 0; j < m; ++j) enqueue(j, np, ctx->d_redk + (int64_t)j * 1024, res + j, s);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(ctx->h_redk, res, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (int j = 0; j < m; ++j) out[j] = ctx->h_redk[j];
+    return PAMG_OK;
+}
+
+int dots_multi(pamg_ctx* ctx, int64_t n, int m, const Cols& x, const Cols& y, double* out) {
+    return reduce_multi(ctx, n, m, out, [&](int j, int np, double* parts, double* res, hipStream_t s) {
+        pamg::launch_dot(n, x.p[j], y.p[j], parts, np, res, s);
+    });
+}
+
+bool cols_ok(const pamg_vec* v) { return v->ncols >= 1 && v->ncols <= kMaxCols; }
+
+// do the allocations of two multi-vectors (or column views) share memory?
+bool overlap(const pamg_vec* a, const pamg_vec* b) {
+    const double* a1 = a->d + (int64_t)a->ncols * a->stride;
+    const double* b1 = b->d + (int64_t)b->ncols * b->stride;
+    return a == b || (a->d < b1 && b->d < a1);
+}
+
+// the checks every multi-column entry point on a matrix shares
+int check_multi_op(pamg_ctx* ctx, const pamg_mat* A, const pamg_vec* X, const pamg_vec* B, const pamg_vec* Y,
+                   const char* who) {
+    if (ctx->nranks > 1) return fail(PAMG_E_STATE, "%s: one part only (SPEC §S13)", who);
+    if (!cols_ok(X) || !cols_ok(Y) || (B && !cols_ok(B))) return fail(PAMG_E_ARG, "%s: need 1..8 columns", who);
+    if (X->ncols != Y->ncols || (B && B->ncols != X->ncols))
+        return fail(PAMG_E_ARG, "%s: the column counts disagree (%d, %d, %d)", who, X->ncols, B ? B->ncols : X->ncols,
+                    Y->ncols);
+    CHECK(check_vec_for(A, X, who));
+    if (Y->n_own != A->nrows || (B && B->n_own != A->nrows)) return fail(PAMG_E_ARG, "%s: size mismatch", who);
+    if (overlap(X, Y) || (B && (overlap(X, B) || overlap(B, Y))))
+        return fail(PAMG_E_ARG, "%s: the multi-vectors must not alias", who);
+    return PAMG_OK;
+}
+
+// the checks the two hierarchy entry points share
+int check_multi_hier(pamg_ctx* ctx, const pamg_hier* H, const pamg_vec* X, const pamg_vec* B, const char* who) {
+    if (ctx->nranks > 1) return fail(PAMG_E_STATE, "%s: one part only (SPEC §S13)", who);
+    if (H->d_perm)
+        return fail(PAMG_E_STATE, "%s: not on a hierarchy with a level-0 permutation (pamg_hier_set_perm)", who);
+    if (!cols_ok(X) || !cols_ok(B)) return fail(PAMG_E_ARG, "%s: need 1..8 columns", who);
+    if (X->ncols != B->ncols)
+        return fail(PAMG_E_ARG, "%s: X has %d columns, B %d", who, X->ncols, B->ncols);
+    CHECK(check_vec_for(H->A[0], X, who));
+    if (B->n_own != H->A[0]->nrows) return fail(PAMG_E_ARG, "%s: B size mismatch", who);
+    if (overlap(X, B)) return fail(PAMG_E_ARG, "%s: X and B must not alias", who);
+    return PAMG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pamg_mvec_create(pamg_ctx* ctx, int64_t n_own, int64_t n_ghost, int ncols, pamg_vec** out) {
+    if (!ctx || !out || n_own < 0 || n_ghost < 0) return fail(PAMG_E_ARG, "mvec_create: bad args");
+    if (ncols < 1 || ncols > kMaxCols) return fail(PAMG_E_ARG, "mvec_create: %d columns outside 1..%d", ncols, kMaxCols);
+    CHECK(set_device(ctx));
+    std::unique_ptr<pamg_vec, int (*)(pamg_vec*)> v(new pamg_vec, pamg_vec_destroy);
+    v->ctx = ctx;
+    ctx_ref(ctx);
+    v->n_own = n_own;
+    v->n_ghost = n_ghost;
+    v->ncols = ncols;
+    v->stride = pamg::mc::col_stride(n_own, n_ghost);
+    CHECK(alloc_cols(ctx, &v->d, ncols, v->stride));
+    *out = v.release();
+    return PAMG_OK;
+}
+
+int pamg_mvec_destroy(pamg_vec* mv) { return pamg_vec_destroy(mv); }
+
+int pamg_mvec_size(const pamg_vec* mv, int64_t* n_own, int64_t* n_ghost, int* ncols, int64_t* stride) {
+    if (!mv) return fail(PAMG_E_ARG, "mvec_size: NULL");
+    if (n_own) *n_own = mv->n_own;
+    if (n_ghost) *n_ghost = mv->n_ghost;
+    if (ncols) *ncols = mv->ncols;
+    if (stride) *stride = mv->stride;
+    return PAMG_OK;
+}
+
+int pamg_mvec_upload(pamg_ctx* ctx, pamg_vec* mv, const double* own) {
+    if (!ctx || !mv || (!own && mv->n_own)) return fail(PAMG_E_ARG, "mvec_upload: bad args");
+    CHECK(set_device(ctx));
+    if (mv->n_own)
+        HIPC(hipMemcpy2DAsync(mv->d, sizeof(double) * mv->stride, own, sizeof(double) * mv->n_own,
+                              sizeof(double) * mv->n_own, mv->ncols, hipMemcpyHostToDevice, ctx->s_comp));
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_mvec_download(pamg_ctx* ctx, const pamg_vec* mv, double* own) {
+    if (!ctx || !mv || (!own && mv->n_own)) return fail(PAMG_E_ARG, "mvec_download: bad args");
+    CHECK(set_device(ctx));
+    if (mv->n_own)
+        HIPC(hipMemcpy2DAsync(own, sizeof(double) * mv->n_own, mv->d, sizeof(double) * mv->stride,
+                              sizeof(double) * mv->n_own, mv->ncols, hipMemcpyDeviceToHost, ctx->s_comp));
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_mvec_column(pamg_vec* mv, int c, pamg_vec** view) {
+    if (!mv || !view) return fail(PAMG_E_ARG, "mvec_column: bad args");
+    if (c < 0 || c >= mv->ncols) return fail(PAMG_E_ARG, "mvec_column: column %d of %d", c, mv->ncols);
+    pamg_vec* v = new pamg_vec;
+    v->ctx = mv->ctx;
+    ctx_ref(mv->ctx);
+    v->n_own = mv->n_own;
+    v->n_ghost = mv->n_ghost;
+    v->d = mv->d + (int64_t)c * mv->stride;
+    v->stride = mv->stride;
+    v->owns = false;
+    *view = v;
+    return PAMG_OK;
+}
+
+int pamg_spmm(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* X, pamg_vec* Y) {
+    if (!ctx || !A || !X || !Y) return fail(PAMG_E_ARG, "spmm: NULL");
+    CHECK(check_multi_op(ctx, A, X, nullptr, Y, "spmm"));
+    CHECK(set_device(ctx));
+    CHECK(apply_multi(ctx, A, pamg::OP_SPMV, X->ncols, cols_of(X), nullptr, cols_of(Y), 0.0));
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_residual_multi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* X, const pamg_vec* B, pamg_vec* R, double* nrm2) {
+    if (!ctx || !A || !X || !B || !R) return fail(PAMG_E_ARG, "residual_multi: NULL");
+    CHECK(check_multi_op(ctx, A, X, B, R, "residual_multi"));
+    CHECK(set_device(ctx));
+    const int k = X->ncols;
+    const Cols b = cols_of(B), r = cols_of(R);
+    CHECK(apply_multi(ctx, A, pamg::OP_RESID, k, cols_of(X), &b, r, 0.0));
+    if (nrm2) {
+        double rr[kMaxCols];
+        CHECK(dots_multi(ctx, R->n_own, k, r, r, rr));
+        for (int c = 0; c < k; ++c) nrm2[c] = std::sqrt(rr[c]);
+    }
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_vcycle_multi(pamg_ctx* ctx, pamg_hier* H, pamg_vec* X, const pamg_vec* B, int ncycles, double* res_hist) {
+    if (!ctx || !H || !X || !B || ncycles < 0 || H->ctx != ctx) return fail(PAMG_E_ARG, "vcycle_multi: bad args");
+    CHECK(check_multi_hier(ctx, H, X, B, "vcycle_multi"));
+    CHECK(set_device(ctx));
+    const int k = X->ncols;
+    if (!res_hist) {
+        CHECK(vcycle_multi_raw(H, k, X->d, X->stride, B->d, B->stride, ncycles, false));
+        HIPC(hipStreamSynchronize(ctx->s_comp));
+        return PAMG_OK;
+    }
+    CHECK(ensure_multi(H, k));
+    // r = b - A x into the level-0 residual columns (a one-level hierarchy has none: a temporary)
+    double* tmp = nullptr;
+    const int64_t n = H->nown[0], rs = H->mc_stride[0];
+    if (H->L == 1) CHECK(alloc_cols(ctx, &tmp, k, rs));
+    const Cols x = cols_of(X), b = cols_of(B), r = cols_of(H->L > 1 ? H->mr[0] : tmp, rs, k);
+    int rc = PAMG_OK;
+    for (int j = 0; j < ncycles && rc == PAMG_OK; ++j) {
+        rc = vcycle_multi_raw(H, k, X->d, X->stride, B->d, B->stride, 1, false);
+        if (rc == PAMG_OK) rc = apply_multi(ctx, H->A[0], pamg::OP_RESID, k, x, &b, r, 0.0);
+        double rr[kMaxCols];
+        if (rc == PAMG_OK) rc = dots_multi(ctx, n, k, r, r, rr);
+        for (int c = 0; c < k && rc == PAMG_OK; ++c) res_hist[(size_t)j * k + c] = std::sqrt(rr[c]);
+    }
+    if (tmp) {
+        (void)hipStreamSynchronize(ctx->s_comp);
+        dfree(tmp);
+    }
+    CHECK(rc);
+    HIPC(hipStreamSynchronize(ctx->s_comp));
+    return PAMG_OK;
+}
+
+int pamg_pcg_multi(pamg_ctx* ctx, pamg_hier* H, pamg_vec* X, const pamg_vec* B, double rtol, int maxit, int* iters,
+                   double* res_hist) {
+    if (!ctx || !H || !X || !B || maxit < 0 || !(rtol >= 0.0) || H->ctx != ctx)
+        return fail(PAMG_E_ARG, "pcg_multi: bad args");
+    CHECK(check_multi_hier(ctx, H, X, B, "pcg_multi"));
+    CHECK(set_device(ctx));
+    const pamg_mat* A = H->A[0];
+    const int k = X->ncols;
+    const int64_t n = A->nrows;
+    CHECK(ensure_multi(H, k));
+    const int64_t ws = H->mc_stride[0];
+    if (!H->mpcg_r)
+        for (double** p : {&H->mpcg_r, &H->mpcg_z, &H->mpcg_p, &H->mpcg_q}) CHECK(alloc_cols(ctx, p, H->mc_cols, ws));
+    hipStream_t s = ctx->s_comp;
+    const Cols x = cols_of(X), b = cols_of(B);
+    const Cols r = cols_of(H->mpcg_r, ws, k), z = cols_of(H->mpcg_z, ws, k), p = cols_of(H->mpcg_p, ws, k),
+               q = cols_of(H->mpcg_q, ws, k);
+    const size_t hl = (size_t)maxit + 1;
+    double rr[kMaxCols], nr0[kMaxCols], rz[kMaxCols], tmp[kMaxCols];
+    int it[kMaxCols] = {};
+    CHECK(apply_multi(ctx, A, pamg::OP_RESID, k, x, &b, r, 0.0));
+    CHECK(dots_multi(ctx, n, k, r, r, rr));
+    // the running columns, in column order; a column leaves when it has stopped (SPEC §S13)
+    int act[kMaxCols], m = 0;
+    for (int c = 0; c < k; ++c) {
+        nr0[c] = std::sqrt(rr[c]);
+        if (res_hist) res_hist[c * hl] = nr0[c];
+        if (nr0[c] > 0.0 && maxit > 0) act[m++] = c;
+    }
+    if (m > 0) {
+        // z = M^-1 r on all k columns (a stopped column rides along, its z is ignored): one graph
+        CHECK(vcycle_multi_raw(H, k, H->mpcg_z, ws, H->mpcg_r, ws, 1, true));
+        for (int j = 0; j < m; ++j)
+            HIPC(hipMemcpyAsync(p.p[act[j]], z.p[act[j]], sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        CHECK(dots_multi(ctx, n, m, subset(r, act, m), subset(z, act, m), tmp));
+        for (int j = 0; j < m; ++j) rz[act[j]] = tmp[j];
+        for (int step = 1; step <= maxit && m > 0; ++step) {
+            const Cols pa = subset(p, act, m), qa = subset(q, act, m), xa = subset(x, act, m), ra = subset(r, act, m);
+            CHECK(apply_multi(ctx, A, pamg::OP_SPMV, m, pa, nullptr, qa, 0.0));
+            CHECK(dots_multi(ctx, n, m, pa, qa, tmp));
+            double alpha[kMaxCols];
+            for (int j = 0; j < m; ++j) alpha[j] = rz[act[j]] / tmp[j];
+            // x += alpha p; r -= alpha q; rr = r.r per column (launch_cg_update's shape), one wait
+            CHECK(reduce_multi(ctx, n, m, tmp, [&](int j, int np, double* parts, double* res, hipStream_t st) {
+                pamg::launch_cg_update(n, alpha[j], pa.p[j], qa.p[j], xa.p[j], ra.p[j], parts, np, res, st);
+            }));
+            int keep = 0;
+            for (int j = 0; j < m; ++j) {
+                const int c = act[j];
+                const double nr = std::sqrt(tmp[j]);
+                it[c] = step;
+                if (res_hist) res_hist[c * hl + step] = nr;
+                if (!(nr <= rtol * nr0[c])) act[keep++] = c;
+            }
+            m = keep;
+            if (m == 0 || step == maxit) break;
+            CHECK(vcycle_multi_raw(H, k, H->mpcg_z, ws, H->mpcg_r, ws, 1, true));
+            CHECK(dots_multi(ctx, n, m, subset(r, act, m), subset(z, act, m), tmp));
+            for (int j = 0; j < m; ++j) {
+                const int c = act[j];
+                const double beta = tmp[j] / rz[c];
+                rz[c] = tmp[j];
+                pamg::launch_axpby(n, 1.0, z.p[c], beta, p.p[c], s);
+            }
+        }
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+    if (iters)
+        for (int c = 0; c < k; ++c) iters[c] = it[c];
+    return PAMG_OK;
+}
+
+int pamg_bench_rowop_multi(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* X, const pamg_vec* B, pamg_vec* Y,
+                           double omega, int reps, double* avg_ms) {
+    const bool known = (op >= 0 && op <= 3) || (op >= 6 && op <= 8);
+    if (!ctx || !A || !X || !Y || reps < 1 || !avg_ms || !known) return fail(PAMG_E_ARG, "bench_rowop_multi: bad args");
+    const bool needs_b = op == pamg::OP_RESID || op == pamg::OP_JACOBI || op >= 6;
+    if (needs_b && !B) return fail(PAMG_E_ARG, "bench_rowop_multi: B needed");
+    if (!needs_b) B = nullptr;
+    CHECK(check_multi_op(ctx, A, X, B, Y, "bench_rowop_multi"));
+    if ((op == pamg::OP_JACOBI || op == pamg::OP_CHEB) && !A->d_diag)
+        return fail(PAMG_E_SETUP, "bench_rowop_multi: jacobi needs a square matrix");
+    if (op == pamg::OP_CHEB && (A->interior.pnc || A->interior.rpat))
+        return fail(PAMG_E_ARG, "bench_rowop_multi: op 6 needs a square operator");
+    if (op >= 7) CHECK(check_block_op(A, "bench_rowop_multi"));
+    if (op == pamg::OP_PROLONG && (A->interior.sym || A->boundary.sym))
+        return fail(PAMG_E_STATE, "bench_rowop_multi: the symmetric layouts have no prolongate-add kernel");
+    CHECK(set_device(ctx));
+    const int k = X->ncols;
+    double* zero = nullptr;  // x_{k-1} of ops 6 and 8
+    const int64_t zs = pamg::mc::col_stride(A->nrows, 0);
+    if (op == pamg::OP_CHEB || op == 8) CHECK(alloc_cols(ctx, &zero, k, zs));
+    const Cols x = cols_of(X), y = cols_of(Y), b = B ? cols_of(B) : Cols{}, xo = zero ? cols_of(zero, zs, k) : Cols{};
+    const int rc = time_reps(ctx->s_comp, reps, avg_ms, [&]() {
+        if (op == 7) return smooth_step_multi(ctx, A, true, plan::SMOOTH, k, &x, b, nullptr, y, 0.0, omega);
+        if (op == 8) return smooth_step_multi(ctx, A, true, plan::CHEB, k, &x, b, &xo, y, omega, omega);
+        return apply_multi(ctx, A, op, k, x, B ? &b : nullptr, y, omega, omega, op == pamg::OP_CHEB ? &xo : nullptr);
+    });
+    dfree(zero);
     return rc;
 }
 

@@ -331,6 +331,75 @@ class PVector:
         _release(self, "pamg_vec_destroy")
 
 
+class MultiVector:
+    """Several right-hand sides (SPEC §S13; ``pamg_mvec_create``): ``ncols`` columns (1..8) of ``n_own`` own
+    values and ``n_ghost`` ghost slots, column-major in one device allocation, every column starting
+    256-byte aligned. Host arrays have shape ``(n_own, ncols)``. One part only."""
+
+    def __init__(self, ctx: Context, n_own: int, ncols: int, n_ghost: int = 0, values=None):
+        h = C.c_void_p()
+        call("pamg_mvec_create", ctx.handle, n_own, n_ghost, int(ncols), C.byref(h))
+        self._h, self.ctx, self.n_own, self.n_ghost, self.ncols = h, ctx, n_own, n_ghost, int(ncols)
+        if values is not None:
+            self.set(values)
+
+    @classmethod
+    def from_numpy(cls, ctx: Context, values, n_ghost: int = 0) -> "MultiVector":
+        values = np.asarray(values, np.float64)
+        if values.ndim != 2:
+            raise ValueError(f"expected an (n, k) array, got shape {values.shape}")
+        return cls(ctx, values.shape[0], values.shape[1], n_ghost, values)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def stride(self) -> int:
+        """Doubles from one column to the next on the device."""
+        s = C.c_int64()
+        call("pamg_mvec_size", self._h, None, None, None, C.byref(s))
+        return s.value
+
+    def set(self, values):
+        values = np.asfortranarray(values, np.float64)
+        if values.shape != (self.n_own, self.ncols):
+            raise ValueError(f"expected shape {(self.n_own, self.ncols)}, got {values.shape}")
+        call("pamg_mvec_upload", self.ctx.handle, self._h, ptr(values))
+
+    def to_numpy(self) -> np.ndarray:
+        out = np.empty((self.n_own, self.ncols), np.float64, order="F")
+        call("pamg_mvec_download", self.ctx.handle, self._h, ptr(out))
+        return out
+
+    def column(self, c: int) -> "PVector":
+        """Column c as a ``PVector`` that aliases it (``pamg_mvec_column``): the whole single-column API
+        works on it; it owns nothing and keeps this multi-vector alive."""
+        h = C.c_void_p()
+        call("pamg_mvec_column", self._h, int(c), C.byref(h))
+        v = PVector.__new__(PVector)
+        v._h, v.ctx, v.n_own, v.n_ghost = h, self.ctx, self.n_own, self.n_ghost
+        v._parent = self
+        return v
+
+    def __del__(self):
+        _release(self, "pamg_mvec_destroy")
+
+
+def spmm(Y: MultiVector, A: "PSparseMatrix", X: MultiVector) -> MultiVector:
+    """Y = A X, column by column with ``mul``'s bits (``pamg_spmm``); a block-row operator streams its
+    matrix once for up to four columns."""
+    call("pamg_spmm", A.ctx.handle, A.handle, X.handle, Y.handle)
+    return Y
+
+
+def residual_multi(R: MultiVector, A: "PSparseMatrix", X: MultiVector, B: MultiVector, with_norm=False):
+    """R = B - A X (``pamg_residual_multi``); with ``with_norm`` returns the ncols norms instead of R."""
+    nrm = np.zeros(X.ncols)
+    call("pamg_residual_multi", A.ctx.handle, A.handle, X.handle, B.handle, R.handle, ptr(nrm) if with_norm else None)
+    return nrm if with_norm else R
+
+
 class PSparseMatrix:
     """Device CSR of one part: own rows, columns local to ``plan`` (own, then ghosts)."""
 
