@@ -197,6 +197,22 @@ int pamg_mat_upload_perm(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, cons
 int pamg_mat_upload_blocked(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, const int64_t* rowptr,
                             const void* col, int col_is_64, const double* val, int index_base,
                             const pamg_plan* col_plan, int bs, pamg_mat** out);
+/* The block-row upload for an operator that may be rectangular, between two node-major spaces of one block
+ * size bs (the prolongations and restrictions of a nodal hierarchy, SPEC §S14; a square operator too). It
+ * goes into the block-row layout (bit 15) where no row has a ghost column and the bs rows of every node
+ * store the same block columns, every touched block whole, in §S3's block-row order; no diagonal is asked
+ * for, and a block row without entries is all padding. SpMV and prolongate-add (and their multi-column
+ * forms, §S13) then run in k_rows_bsr / k_rows_bsr_mc with the bits of the CSR row sums. Anything else
+ * uploads in the layouts pamg_mat_upload gives it; bit 15 tells which happened. An operator with fewer rows
+ * than own columns (a restriction: few, long block rows) takes the layout's row-per-lane form (k_rows_bsr_r:
+ * a lane per scalar row, bs times the lanes, the same bits; out[6] = 1); PAMG_BSR_ROW_LANES=0 or =1 in the
+ * environment, read at each upload, overrides that rule (A/B measurements and tests). The operations that read
+ * a diagonal (Jacobi, Chebyshev, the block sweeps) stay argument errors on an operator that is not square.
+ * bs = 1 is pamg_mat_upload. PAMG_E_ARG for bs outside 1..4 and, with bs > 1, for nrows % bs != 0 or own
+ * columns that are not a multiple of bs. */
+int pamg_mat_upload_block_rows(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, const int64_t* rowptr,
+                               const void* col, int col_is_64, const double* val, int index_base,
+                               const pamg_plan* col_plan, int bs, pamg_mat** out);
 int pamg_mat_destroy(pamg_mat* A);
 int pamg_mat_info(const pamg_mat* A, int64_t* nrows, int64_t* ncols_local, int64_t* nnz);
 /* Bytes of matrix data one row operation streams in the layout chosen at upload: 8 B values +
@@ -232,8 +248,10 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes);
  * (pnc_compact; out[4] = the combinations); bit 13: with bit 9, one index byte per nonzero names an
  * (offset, value) pair of the group (ell_pair); bit 14: with bit 10, the grid cuts into whole tiles
  * and "pnc" = 1 launches the tiled march (k_rows_pnct) for it (out[8] is the grid of either march);
- * bit 15: the set runs in the block-row layout (bsr; pamg_mat_upload_blocked: then out[3] = the block
- * size, out[4] = the padded block slots, out[8] = the kernel's grid). */
+ * bit 15: the set runs in the block-row layout (bsr; pamg_mat_upload_blocked, pamg_mat_upload_block_rows:
+ * then out[3] = the block size, out[4] = the padded block slots, out[8] = the kernel's grid, and out[6] = 1
+ * where a restriction-shaped operator took the row-per-lane form — a lane per scalar row, the slots per
+ * row with bs values each). */
 int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
 /* The windowed sliced-ELL layout of a matrix (ell_xwin; with pamg_mat_layout bits 9 and 13): out[0]
  * 1 where the matrix runs in it (else all 0), out[1] the groups whose x window is staged in LDS,
@@ -581,6 +599,20 @@ int pamg_setup_cholinv(const pamg_hcsr* A, double* ainv_colmajor);
  * multiples of bs; PAMG_E_SETUP for a block that is not positive definite (the message names it). */
 int pamg_setup_block_diag(const pamg_hcsr* A, int64_t row0, int bs, double* blocks, double* inv,
                           double* rho_b);
+/* Node matrix of the own rows of a node-blocked operator (SPEC §S14; A's rows are global rows row0..):
+ * one entry per stored bs x bs block (m, c), its Frobenius norm (squares summed from +0.0, d outer and e
+ * inner, then one sqrt), rows = own nodes, columns = global node ids, ascending. pamg_setup_aggregate on
+ * N (row0 / bs, the same theta) gives the node aggregates. PAMG_E_ARG, the message naming the first
+ * offending node, where A is not node-blocked (the bs rows of a node store the same block columns, each
+ * block whole, in §S3's block-row order, the diagonal block among them), for bs outside 2..4 and for
+ * nrows or row0 not multiples of bs; PAMG_E_SETUP for a diagonal block that is all zero. The invariant
+ * (§S14): with node aggregates every A_l, P_l and R_l of the hierarchy is node-blocked again. */
+int pamg_setup_node_matrix(const pamg_hcsr* A, int64_t row0, int bs, pamg_hcsr** N);
+/* Tentative prolongator rows of nb own nodes (SPEC §S14): row bs m + d has the single entry
+ * T[bs m + d, bs (coarse0_nodes + agg[m]) + d] = 1/sqrt(|agg|); the rows of an isolated node (-1) are
+ * empty. ncols_global counts scalar columns (a multiple of bs). PAMG_E_ARG for bs outside 2..4. */
+int pamg_setup_tentative_nodal(int64_t nb, const int32_t* agg, int64_t n_agg, int64_t coarse0_nodes,
+                               int64_t ncols_global, int bs, pamg_hcsr** out);
 
 #ifdef __cplusplus
 }

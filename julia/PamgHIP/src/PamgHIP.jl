@@ -354,7 +354,7 @@ mutable struct DeviceMatrix
 end
 """
     DeviceMatrix(ctx, rowptr, col, val, ncols_local; plan = nothing, index_base = 1,
-                 row_perm = nothing, col_perm = nothing, block_size = 1)
+                 row_perm = nothing, col_perm = nothing, block_size = 1, block_rows = 1)
 
 One part's own rows in CSR with LOCAL column ids (own columns first, then the plan's ghost
 slots), each row in ascending global column order (SPEC §S1). Int64 or Int32 columns, 1- or
@@ -364,15 +364,19 @@ device own column k is own column col_perm[k]; rows keep their storage order (sa
 `block_size` > 1 (pamg_mat_upload_blocked; not with a permutation): a square node-major operator of
 that many unknowns per node takes the block-row layout where every node's rows store the same whole
 blocks and no row has a ghost column (`layout(A).bsr`; same bits), else the layouts of a plain upload.
+`block_rows` > 1 (pamg_mat_upload_block_rows): the same for an operator that may be rectangular, between
+two node-major spaces of that block size — the P and R of a nodal hierarchy (SPEC §S14); no diagonal is asked.
 """
 function DeviceMatrix(ctx::Context, rowptr::AbstractVector{<:Integer}, col::AbstractVector{<:Integer},
                       val::AbstractVector{<:Real}, ncols_local::Integer;
                       plan::Union{Nothing,ExchangePlan} = nothing, index_base::Integer = 1,
                       row_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing,
                       col_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing,
-                      block_size::Integer = 1)
-    block_size != 1 && (row_perm !== nothing || col_perm !== nothing) &&
+                      block_size::Integer = 1, block_rows::Integer = 1)
+    (block_size != 1 || block_rows != 1) && (row_perm !== nothing || col_perm !== nothing) &&
         throw(ArgumentError("DeviceMatrix: block_size > 1 cannot be combined with row_perm / col_perm"))
+    block_size != 1 && block_rows != 1 &&
+        throw(ArgumentError("DeviceMatrix: give block_size (square operators) or block_rows, not both"))
     rp = Vector{Int64}(rowptr)
     c = eltype(col) == Int32 ? Vector{Int32}(col) : Vector{Int64}(col)
     is64 = eltype(c) == Int64 ? Cint(1) : Cint(0)
@@ -384,6 +388,12 @@ function DeviceMatrix(ctx::Context, rowptr::AbstractVector{<:Integer}, col::Abst
                      Ptr{Ptr{Cvoid}}),
                     ctx.h, length(rp) - 1, ncols_local, rp, c, is64, v, index_base,
                     plan === nothing ? C_NULL : plan.h, block_size, h))
+    elseif block_rows != 1
+        check(ccall((:pamg_mat_upload_block_rows, libpamg), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Cvoid}, Cint,
+                     Ptr{Ptr{Cvoid}}),
+                    ctx.h, length(rp) - 1, ncols_local, rp, c, is64, v, index_base,
+                    plan === nothing ? C_NULL : plan.h, block_rows, h))
     elseif row_perm === nothing && col_perm === nothing
         check(ccall((:pamg_mat_upload, libpamg), Cint,
                     (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}),
@@ -896,6 +906,20 @@ function tentative(agg::Vector{Int32}, nagg::Integer, coarse0::Integer, ncols_gl
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:pamg_setup_tentative, libpamg), Cint, (Int64, Ptr{Int32}, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}),
                 length(agg), agg, nagg, coarse0, ncols_global, h))
+    HostCSR(h[])
+end
+"The node matrix of a node-blocked operator's own rows (SPEC §S14): one Frobenius norm per stored bs x bs block."
+function node_matrix(A::HostCSR, row0::Integer, bs::Integer)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pamg_setup_node_matrix, libpamg), Cint, (Ptr{Cvoid}, Int64, Cint, Ptr{Ptr{Cvoid}}), A.h, row0, bs, h))
+    HostCSR(h[])
+end
+"Tentative prolongator of node aggregates (SPEC §S14): `agg` holds one aggregate id per own node."
+function tentative_nodal(agg::Vector{Int32}, nagg::Integer, coarse0_nodes::Integer, ncols_global::Integer, bs::Integer)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pamg_setup_tentative_nodal, libpamg), Cint,
+                (Int64, Ptr{Int32}, Int64, Int64, Int64, Cint, Ptr{Ptr{Cvoid}}),
+                length(agg), agg, nagg, coarse0_nodes, ncols_global, bs, h))
     HostCSR(h[])
 end
 "C = X * Y with Y's own rows from y0 and its ghost rows `Yghost` (global ids `ghost_ids`, ascending)."

@@ -80,6 +80,7 @@ SIGNATURES = {
     "pamg_mat_upload": [vp, i64, i64, vp, vp, i32, vp, i32, vp, pvp],
     "pamg_mat_upload_perm": [vp, i64, i64, vp, vp, i32, vp, i32, vp, vp, vp, pvp],
     "pamg_mat_upload_blocked": [vp, i64, i64, vp, vp, i32, vp, i32, vp, i32, pvp],
+    "pamg_mat_upload_block_rows": [vp, i64, i64, vp, vp, i32, vp, i32, vp, i32, pvp],
     "pamg_mat_destroy": [vp],
     "pamg_mat_info": [vp, pi64, pi64, pi64],
     "pamg_mat_stream_bytes": [vp, pi64],
@@ -151,6 +152,8 @@ SIGNATURES = {
     "pamg_setup_hstack_rows": [i32, vp, pvp],
     "pamg_setup_cholinv": [vp, vp],
     "pamg_setup_block_diag": [vp, i64, i32, vp, vp, pdbl],
+    "pamg_setup_node_matrix": [vp, i64, i32, pvp],
+    "pamg_setup_tentative_nodal": [i64, vp, i64, i64, i64, i32, pvp],
 }
 _RESTYPE = {"pamg_version": C.c_char_p, "pamg_last_error": C.c_char_p}
 
@@ -261,7 +264,9 @@ def layout_of(M, part_set: int = 0) -> dict:
             "ell": bool(out[9] & 512), "pnc": bool(out[9] & 1024),
             "rpat": bool(out[9] & 2048), "pnc_compact": bool(out[9] & 4096),
             "ell_pair": bool(out[9] & 8192), "pnc_tiled": bool(out[9] & 16384),
-            "bsr": bool(out[9] & 32768)}  # (ell_xwin*: pamg_mat_ell_window)
+            "bsr": bool(out[9] & 32768),
+            # with bsr: the row-per-lane form (a lane per scalar row: restriction-shaped block-row operators)
+            "bsr_row_lanes": bool(out[9] & 32768) and out[6] == 1}  # (ell_xwin*: pamg_mat_ell_window)
 
 
 def last_error() -> str:

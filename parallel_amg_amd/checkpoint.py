@@ -76,7 +76,8 @@ def save_hierarchy(H: HostHierarchy, path: str) -> None:
     d = {"version": np.int64(_VERSION), "nparts": np.int64(H.nparts), "nlevels": np.int64(H.nlevels),
          "parts": np.asarray(sorted(H.levels[0]), np.int64), "ainv": np.asarray(H.ainv, np.float64),
          "n_coarse": np.int64(H.n_coarse), "rep_level": np.int64(H.rep_level),
-         "rep_offsets": np.asarray(H.rep_offsets if H.rep_offsets is not None else [], np.int64)}
+         "rep_offsets": np.asarray(H.rep_offsets if H.rep_offsets is not None else [], np.int64),
+         "block_size": np.int64(getattr(H, "block_size", 1))}
     for l, lev in enumerate(H.levels):
         for p, lp in lev.items():
             k = f"l{l}_p{p}"
@@ -120,4 +121,5 @@ def load_hierarchy(path: str, backend=None) -> HostHierarchy:
             levels.append(lev)
         ro = z["rep_offsets"]
         return HostHierarchy(int(z["nparts"]), parts, levels, z["ainv"], int(z["n_coarse"]),
-                             rep_level=int(z["rep_level"]), rep_offsets=ro if len(ro) else None)
+                             rep_level=int(z["rep_level"]), rep_offsets=ro if len(ro) else None,
+                             block_size=int(z["block_size"]) if "block_size" in z else 1)

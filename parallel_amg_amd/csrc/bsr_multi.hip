@@ -156,10 +156,136 @@ void launch_chunk_op(const pamg_mat& A, int op, int fuse, const double* const* x
     }
 }
 
+// ------------------------------------------------------------------ the row-per-lane form (BsrSet::row_lanes)
+// k_rows_bsr_r: one lane per SCALAR row of a restriction-shaped block-row operator (SPEC §S14: R has few,
+// long block rows — about 125 blocks per coarse node on a 27-point grid and nb / 27 nodes — so a lane per node
+// leaves most of the machine idle). One slice of kEllW rows per wave, kBsrSlices slices per workgroup; the BS
+// rows of a node sit in BS adjacent lanes. Per slot a lane loads the block column, its own row's BS values
+// (adjacent doubles, 16-byte loads for BS 2 and 4: the wave reads one contiguous run of 512 BS bytes) and,
+// per column of the launch, the block's BS entries of x — the lanes of a node read the same line — and adds
+// s = s + v_e x_e in e order, each product and each add rounded once: row BS m + d's stored order, so §S3's
+// bits. Row sums are never split over lanes. Slots go four at a time, the columns and values of a group
+// loaded before its first product (a padded slot holds column -1 and zeros: its loads are in bounds, its
+// products are skipped), so four dependent x loads are in flight per lane instead of one. No LDS, no barrier.
+// OP_SPMV, OP_RESID and OP_PROLONG only: the form is built for operators that are not square.
+template <int BS>
+__device__ __forceinline__ void bsr_r_load_v(const double* __restrict__ p, double (&v)[BS]) {
+    if constexpr (BS == 3) {
+        v[0] = p[0];
+        v[1] = p[1];
+        v[2] = p[2];
+    } else {
+#pragma unroll
+        for (int e = 0; e < BS; e += 2) {
+            const double2 t = *reinterpret_cast<const double2*>(p + e);
+            v[e] = t.x;
+            v[e + 1] = t.y;
+        }
+    }
+}
+
+template <int BS, int OP, int NV>
+__global__ __launch_bounds__(kBlock) void k_rows_bsr_r(int nrows, int ns, const int64_t* __restrict__ soff,
+                                                       const int* __restrict__ bcol, const double* __restrict__ val,
+                                                       int x16, McIn<NV> x, McIn<NV> b, McOut<NV> y) {
+    constexpr int U = 4;
+    const int lane = threadIdx.x & (kEllW - 1);
+    const int sl = blockIdx.x * kBsrSlices + (threadIdx.x >> 6);
+    if (sl >= ns) return;
+    const int64_t k0 = soff[sl], k1 = soff[sl + 1];
+    const int r = sl * kEllW + lane;
+    double s[NV];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) s[c] = 0.0;
+    const int* cp = bcol + k0 * kEllW + lane;
+    const double* vp = val + (k0 * kEllW + lane) * BS;
+    auto slot = [&](int col, const double (&v)[BS]) {
+        if (col < 0) return;
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            double xe[BS];
+            bsr_load_x<BS>(x.p[c], col, x16 != 0, xe);
+#pragma unroll
+            for (int e = 0; e < BS; ++e) {
+                const double p = v[e] * xe[e];
+                s[c] = s[c] + p;
+            }
+        }
+    };
+    int64_t k = k0;
+    for (; k + U <= k1; k += U, cp += U * kEllW, vp += U * kEllW * BS) {
+        int col[U];
+        double v[U][BS];
+#pragma unroll
+        for (int u = 0; u < U; ++u) col[u] = cp[u * kEllW];
+#pragma unroll
+        for (int u = 0; u < U; ++u) bsr_r_load_v<BS>(vp + u * kEllW * BS, v[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) slot(col[u], v[u]);
+    }
+    for (; k < k1; ++k, cp += kEllW, vp += kEllW * BS) {
+        double v[BS];
+        bsr_r_load_v<BS>(vp, v);
+        slot(*cp, v);
+    }
+    if (r >= nrows) return;
+#pragma unroll
+    for (int c = 0; c < NV; ++c) epilogue<OP>(r, s[c], x.p[c], b.p[c], y.p[c], 0.0, 1.0);
+}
+
+template <int OP, int NV>
+void launch_rows_chunk(const pamg_mat& A, const double* const* x, const double* const* b, double* const* y,
+                       hipStream_t s) {
+    const BsrSet& B = A.bsr;
+    McIn<NV> xa, ba;
+    McOut<NV> ya;
+    int x16 = 1;
+    for (int c = 0; c < NV; ++c) {
+        xa.p[c] = x[c];
+        ba.p[c] = b ? b[c] : nullptr;
+        ya.p[c] = y[c];
+        if ((reinterpret_cast<uintptr_t>(x[c]) & 15) != 0) x16 = 0;
+    }
+    auto go = [&](auto kern) {
+        kern<<<B.grid, kBlock, 0, s>>>((int)A.nrows, (int)B.nslices, B.d_soff, B.d_bcol, B.d_val, x16, xa, ba, ya);
+    };
+    switch (B.bs) {
+        case 2: go(k_rows_bsr_r<2, OP, NV>); break;
+        case 3: go(k_rows_bsr_r<3, OP, NV>); break;
+        default: go(k_rows_bsr_r<4, OP, NV>); break;
+    }
+}
+
+template <int NV>
+void launch_rows_chunk_op(const pamg_mat& A, int op, const double* const* x, const double* const* b, double* const* y,
+                          hipStream_t s) {
+    switch (op) {
+        case OP_SPMV: launch_rows_chunk<OP_SPMV, NV>(A, x, b, y, s); break;
+        case OP_RESID: launch_rows_chunk<OP_RESID, NV>(A, x, b, y, s); break;
+        case OP_PROLONG: launch_rows_chunk<OP_PROLONG, NV>(A, x, b, y, s); break;
+        default: break;  // (the diagonal ops are refused before: the operator is not square)
+    }
+}
+
 }  // namespace
+
+void launch_bsr_rows(const pamg_mat& A, int op, int ncols, const double* const* x, const double* const* b,
+                     double* const* y, hipStream_t s) {
+    if (!A.bsr.row_lanes || A.nrows <= 0) return;
+    int first[mc::kMaxCols], width[mc::kMaxCols];
+    const int n = mc::chunks(ncols, first, width);
+    for (int i = 0; i < n; ++i) {
+        const int c = first[i];
+        const double* const* bc = b ? b + c : nullptr;
+        if (width[i] == 4) launch_rows_chunk_op<4>(A, op, x + c, bc, y + c, s);
+        else if (width[i] == 2) launch_rows_chunk_op<2>(A, op, x + c, bc, y + c, s);
+        else launch_rows_chunk_op<1>(A, op, x + c, bc, y + c, s);
+    }
+}
 
 void launch_bsr_multi(const pamg_mat& A, int op, int fuse, int ncols, const double* const* x, const double* const* b,
                       const double* const* xold, double* const* y, double omega, double c1, hipStream_t s) {
+    if (A.interior.bsr_r) return launch_bsr_rows(A, op, ncols, x, b, y, s);
     if (A.bsr.nb <= 0) return;
     int first[mc::kMaxCols], width[mc::kMaxCols];
     const int n = mc::chunks(ncols, first, width);
@@ -175,7 +301,7 @@ void launch_bsr_multi(const pamg_mat& A, int op, int fuse, int ncols, const doub
             launch_bsr_block(A, fuse == 1 ? BM_JACOBI : BM_CHEB, x[c], b[c], oc ? oc[0] : nullptr, y[c], c1, omega, s);
         } else {
             const double* xo = op == OP_CHEB ? (oc ? oc[0] : nullptr) : x[c];
-            launch_rows(A, A.interior, op, x[c], bc ? bc[0] : nullptr, xo, y[c], omega, s, c1);
+            launch_set(A, A.interior, op, x[c], bc ? bc[0] : nullptr, xo, y[c], omega, s, c1);
         }
     }
 }

@@ -272,6 +272,7 @@ struct Upload {
     const std::function<int64_t()>& band;  // the banded tile order's row distance, computed on first use
     UploadTrace& tr;
     int bs = 1;                      // > 1: uploaded through pamg_mat_upload_blocked (bsr_try)
+    bool rect = false;               // with bs > 1: through pamg_mat_upload_block_rows (any shape, no diagonal asked)
 };
 // Every family provides four functions. X_try holds the family's eligibility rule and its
 // builder: where it takes the rows it sets its TileSet flag on A->interior and clears
@@ -1873,12 +1874,15 @@ void pnc_free(pamg::PncSet& P) {
 
 // ------------------------------------------------------------------ bsr
 
-// Block-row layout (pamg::BsrSet, k_rows_bsr) of a matrix uploaded through pamg_mat_upload_blocked, when it
+// Block-row layout (pamg::BsrSet, k_rows_bsr) of a matrix uploaded through pamg_mat_upload_blocked or
+// pamg_mat_upload_block_rows (shared: the operator may be rectangular, a block row may be empty), when it
 // qualifies: the bs rows of every node store the same block columns c_0 < c_1 < ..., row bs m + d as the
 // entries bs c_0, bs c_0 + 1, ..., bs c_0 + bs - 1, bs c_1, ... in that storage order — every touched block
 // whole, and the kernel's walk "blocks in order, e = 0 .. bs - 1 inside" the row's stored order (SPEC §S3).
 // Otherwise nothing is built.
-int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs) {
+// row_lanes: the row-per-lane form (BsrSet::row_lanes, TileSet::bsr_r) instead of one lane per node.
+int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs);
+int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs, bool row_lanes = false) {
     using pamg::kEllW;
     pamg_ctx* ctx = A->ctx;
     const int64_t nb = A->nrows / bs, ns = (nb + kEllW - 1) / kEllW;
@@ -1898,6 +1902,7 @@ int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
         }
     });
     if (!ok) return PAMG_OK;
+    if (row_lanes) return build_bsr_rows(A, rp, ci, val, bs);
     pamg::BsrSet& B = A->bsr;
     std::vector<int64_t> soff(ns + 1, 0);
     for (int64_t s = 0; s < ns; ++s) {
@@ -1936,13 +1941,69 @@ int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
     return PAMG_OK;
 }
 
-// a square operator with a nonzero diagonal in every row and no ghost column, in whole nodes
+// The row-per-lane form of a matrix build_bsr has checked: a sliced ELL over scalar rows, a block column and
+// the row's bs entries of the block per slot (pamg_device.h, BsrSet).
+int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs) {
+    using pamg::kEllW;
+    pamg_ctx* ctx = A->ctx;
+    const int64_t n = A->nrows, ns = (n + kEllW - 1) / kEllW;
+    pamg::BsrSet& B = A->bsr;
+    std::vector<int64_t> soff(ns + 1, 0);
+    for (int64_t s = 0; s < ns; ++s) {
+        int64_t w = 0;
+        for (int64_t i = s * kEllW; i < std::min(n, (s + 1) * kEllW); ++i) w = std::max(w, (rp[i + 1] - rp[i]) / bs);
+        soff[s + 1] = soff[s] + w;
+    }
+    const int64_t slots = soff[ns] * kEllW;
+    if (slots >= INT32_MAX) return PAMG_OK;  // (pamg_mat_layout reports the slots as an int)
+    std::vector<int> bcol((size_t)slots, -1);
+    std::vector<double> bval((size_t)(slots * bs), 0.0);
+    par_for(n, [&](int64_t a, int64_t b) {
+        for (int64_t i = a; i < b; ++i) {
+            const int64_t s = i / kEllW, l = i % kEllW, nblk = (rp[i + 1] - rp[i]) / bs;
+            for (int64_t k = 0; k < nblk; ++k) {
+                const int64_t at = (soff[s] + k) * kEllW + l;
+                bcol[at] = ci[rp[i] + k * bs] / bs;
+                for (int e = 0; e < bs; ++e) bval[at * bs + e] = val[rp[i] + k * bs + e];
+            }
+        }
+    });
+    CHECK(dalloc(&B.d_soff, ns + 1));
+    CHECK(dalloc(&B.d_bcol, std::max<int64_t>(slots, 1)));
+    CHECK(dalloc(&B.d_val, std::max<int64_t>(slots * bs, 2)));
+    CHECK(h2d(ctx, B.d_soff, soff.data(), sizeof(int64_t) * (ns + 1)));
+    CHECK(h2d(ctx, B.d_bcol, bcol.data(), sizeof(int) * bcol.size()));
+    CHECK(h2d(ctx, B.d_val, bval.data(), sizeof(double) * bval.size()));
+    B.bs = bs;
+    B.nb = n / bs;
+    B.nslices = ns;
+    B.slots = slots;
+    B.grid = (int)((ns + pamg::kBsrSlices - 1) / pamg::kBsrSlices);
+    B.row_lanes = true;
+    A->interior.bsr_r = true;
+    return PAMG_OK;
+}
+
+// Which form a restriction-shaped operator of pamg_mat_upload_block_rows takes: the row-per-lane one (the
+// measured choice, DESIGN.md "Nodal hierarchy"), unless PAMG_BSR_ROW_LANES=0 in the environment asks for a
+// lane per node (=1: the row-per-lane form; read at every upload; for A/B measurements and the tests).
+constexpr bool kBsrRowLanes = true;
+bool bsr_row_lanes() {
+    const char* e = std::getenv("PAMG_BSR_ROW_LANES");
+    if (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) return e[0] == '1';
+    return kBsrRowLanes;
+}
+
+// a square operator with a nonzero diagonal in every row and no ghost column, in whole nodes; through
+// pamg_mat_upload_block_rows (u.rect) any shape between two node-major spaces, no diagonal asked for
 int bsr_try(Upload& u) {
     pamg_mat* A = u.A;
-    if (u.bs > 1 && u.n_own_cols == A->nrows && u.has_all_diag && u.bnd.empty() && A->nrows > 0 &&
-        A->nrows % u.bs == 0) {
-        CHECK(build_bsr(A, u.rp, u.ci, u.val, u.bs));
-        if (A->interior.bsr) u.inner.clear();  // the rows run in k_rows_bsr, not in tiles
+    const bool shape = u.rect ? u.n_own_cols % u.bs == 0 : u.n_own_cols == A->nrows && u.has_all_diag;
+    if (u.bs > 1 && shape && u.bnd.empty() && A->nrows > 0 && A->nrows % u.bs == 0) {
+        // (few, long block rows: a lane per scalar row where that form is wanted)
+        const bool row_lanes = u.rect && A->nrows < u.n_own_cols && bsr_row_lanes();
+        CHECK(build_bsr(A, u.rp, u.ci, u.val, u.bs, row_lanes));
+        if (pamg::bsr_any(*A)) u.inner.clear();  // the rows run in k_rows_bsr / k_rows_bsr_r, not in tiles
         u.tr.mark("bsr");
     }
     return PAMG_OK;
@@ -1950,14 +2011,16 @@ int bsr_try(Upload& u) {
 
 // the padded stream: a column and bs^2 values per block slot, the slice offsets
 int64_t bsr_bytes(const pamg_mat* A) {
-    if (!A->interior.bsr) return 0;
-    return A->bsr.slots * (4 + 8 * (int64_t)A->bsr.bs * A->bsr.bs) + 8 * (A->bsr.nslices + 1);
+    if (!pamg::bsr_any(*A)) return 0;
+    const int64_t per_slot = A->bsr.row_lanes ? A->bsr.bs : (int64_t)A->bsr.bs * A->bsr.bs;
+    return A->bsr.slots * (4 + 8 * per_slot) + 8 * (A->bsr.nslices + 1);
 }
 
 void bsr_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
-    if (!t.bsr) return;
+    if (!t.bsr && !t.bsr_r) return;
     out[3] = A->bsr.bs;  // the block size, the padded block slots, k_rows_bsr's grid
     out[4] = (int)A->bsr.slots;
+    out[6] = t.bsr_r ? 1 : 0;  // the row-per-lane form: the slots are per scalar row (bs values each)
     out[8] = A->bsr.grid;
     out[9] |= 32768;
 }
@@ -2727,7 +2790,7 @@ int tiles_try(Upload& u) {
 int64_t tiles_bytes(const pamg_mat* A) {
     int64_t sum = 0;
     for (const pamg::TileSet* t : {&A->interior, &A->boundary}) {
-        if (t->sym || t->ell || t->pnc || t->rpat || t->bsr) continue;  // counted by their families
+        if (t->sym || t->ell || t->pnc || t->rpat || t->bsr || t->bsr_r) continue;  // counted by their families
         const int64_t ns = t->n_short, nz = t->nnz_short;
         int64_t b = 8 * (int64_t)t->n_long + 12 * t->nnz_long;
         const bool base = t->c24 && !t->cd;
@@ -2788,10 +2851,11 @@ void tiles_free(pamg::TileSet& ts) {
     ts.n_short = ts.n_long = 0;
 }
 
-// pamg_mat_upload (bs = 1) and pamg_mat_upload_blocked (bs > 1, its arguments checked): the block-row
-// family is tried first for the latter alone; where it declines the matrix goes on exactly as bs = 1 does
+// pamg_mat_upload (bs = 1), pamg_mat_upload_blocked and pamg_mat_upload_block_rows (bs > 1, their arguments
+// checked; rect: the latter): the block-row family is tried first for those two alone; where it declines the
+// matrix goes on exactly as bs = 1 does
 int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr, const void* col, int col_is_64,
-               const double* val, int index_base, const pamg_plan* plan, int bs, pamg_mat** out) {
+               const double* val, int index_base, const pamg_plan* plan, int bs, pamg_mat** out, bool rect = false) {
     if (!ctx || !out || nrows < 0 || ncols < 0 || !rowptr || (index_base != 0 && index_base != 1))
         return fail(PAMG_E_ARG, "mat_upload: bad args");
     const int64_t nnz = rowptr[nrows] - index_base;
@@ -2926,9 +2990,9 @@ int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowpt
     };
     // the layout families in their fixed order: each takes the interior rows left (and clears the
     // list) or declines
-    Upload u{A.get(), rp, ci, val, n_own_cols, has_all_diag, inner, bnd, get_band, tr, bs};
+    Upload u{A.get(), rp, ci, val, n_own_cols, has_all_diag, inner, bnd, get_band, tr, bs, rect};
     CHECK(bsr_try(u));
-    if (!A->interior.bsr) {
+    if (!pamg::bsr_any(*A)) {
         CHECK(sym_try(u));
         CHECK(rpat_try(u));
         CHECK(ell_try(u));
@@ -2987,6 +3051,21 @@ int pamg_mat_upload_blocked(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const i
             return fail(PAMG_E_ARG, "mat_upload_blocked: %lld rows are not whole blocks of %d", (long long)nrows, bs);
     }
     return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, bs, out);
+}
+
+int pamg_mat_upload_block_rows(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr,
+                               const void* col, int col_is_64, const double* val, int index_base,
+                               const pamg_plan* plan, int bs, pamg_mat** out) {
+    if (bs < 1 || bs > 4) return fail(PAMG_E_ARG, "mat_upload_block_rows: block size %d outside 1..4", bs);
+    if (bs > 1 && ctx && nrows >= 0 && ncols >= 0) {
+        const int64_t n_own_cols = plan ? plan->n_own : ncols;
+        if (nrows % bs != 0)
+            return fail(PAMG_E_ARG, "mat_upload_block_rows: %lld rows are not whole blocks of %d", (long long)nrows, bs);
+        if (n_own_cols % bs != 0)
+            return fail(PAMG_E_ARG, "mat_upload_block_rows: %lld own columns are not whole blocks of %d",
+                        (long long)n_own_cols, bs);
+    }
+    return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, bs, out, bs > 1);
 }
 
 // Locality permutation inside the device layout: device row i = caller row row_perm[i], own

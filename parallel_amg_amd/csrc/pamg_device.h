@@ -111,6 +111,10 @@ struct TileSet {
     // block-row layout (pamg_mat::bsr; the whole of a square node-major operator uploaded through
     // pamg_mat_upload_blocked): the rows run in k_rows_bsr instead of tiles
     bool bsr = false;
+    // the block-row layout's row-per-lane form (pamg_mat::bsr with BsrSet::row_lanes; a restriction-shaped
+    // operator uploaded through pamg_mat_upload_block_rows): the rows run in k_rows_bsr_r (bsr_multi.hip)
+    // through launch_set, never in launch_rows
+    bool bsr_r = false;
     int max_short_len = 0;    // longest row in a short tile
     int64_t rows_short = 0;   // rows covered by the short tiles
     int64_t nnz_short = 0, nnz_long = 0;  // nonzeros covered by the tiles / the long rows
@@ -363,6 +367,15 @@ struct RpatSet {
 // block's entry (d, e) at d_val[((d_soff[s] + k) * bs * bs + d * bs + e) * kEllW + l]. One column index per
 // block: 8 + 4 / bs^2 bytes per stored nonzero; x is gathered once per block as bs adjacent doubles; a
 // lane holds its node's bs row sums in registers (the fused block smoothers of SPEC §S12).
+//
+// Through pamg_mat_upload_block_rows the operator may be rectangular (a block column c reads x[bs c ..
+// bs c + bs - 1] of the column space; an empty block row is all padding), and a restriction-shaped one —
+// fewer rows than own columns: few, long block rows — takes the row-per-lane form (row_lanes; k_rows_bsr_r):
+// a sliced ELL over SCALAR rows, slice s the kEllW rows from kEllW s, so the bs rows of a node sit in bs
+// adjacent lanes and every row sum is still one lane's (SPEC §S3). Slot k of slice s, lane l: the block
+// column at d_bcol[(d_soff[s] + k) * kEllW + l] (-1: padding), the row's bs entries of that block at
+// d_val[((d_soff[s] + k) * kEllW + l) * bs + e] — bs adjacent doubles per lane, contiguous over the wave.
+// 8 + 4 / bs bytes per stored nonzero, bs times the lanes of the node-per-lane form.
 constexpr int kBsrSlices = kBlock / kEllW;  // slices (waves) per workgroup
 struct BsrSet {
     int bs = 0;
@@ -372,6 +385,7 @@ struct BsrSet {
     int* d_bcol = nullptr;        // slots
     double* d_val = nullptr;      // slots * bs * bs
     int grid = 0;                 // workgroups of k_rows_bsr
+    bool row_lanes = false;       // the row-per-lane form: nslices, slots and the arrays are per scalar row
 };
 
 struct SymDia {
@@ -578,6 +592,17 @@ void launch_bsr_block(const pamg_mat& A, int mode, const double* x, const double
 // where the operation reads none; an entry of xold may be null (zeros).
 void launch_bsr_multi(const pamg_mat& A, int op, int fuse, int ncols, const double* const* x, const double* const* b,
                       const double* const* xold, double* const* y, double omega, double c1, hipStream_t s);
+// bsr_multi.hip: OP_SPMV, OP_RESID or OP_PROLONG of an operator in the row-per-lane block-row form
+// (A.interior.bsr_r; never square, so no other op reaches it) on ncols columns, cut like launch_bsr_multi's.
+void launch_bsr_rows(const pamg_mat& A, int op, int ncols, const double* const* x, const double* const* b,
+                     double* const* y, hipStream_t s);
+inline bool bsr_any(const pamg_mat& A) { return A.interior.bsr || A.interior.bsr_r; }
+// The rows of one set of A, whatever their layout: launch_rows, or k_rows_bsr_r for the row-per-lane form.
+inline void launch_set(const pamg_mat& A, const TileSet& ts, int op, const double* x, const double* b,
+                       const double* xold, double* y, double omega, hipStream_t s, double c1 = 0.0) {
+    if (ts.bsr_r) launch_bsr_rows(A, op, 1, &x, b ? &b : nullptr, &y, s);
+    else launch_rows(A, ts, op, x, b, xold, y, omega, s, c1);
+}
 // SPEC §S12 estimate step after y = A v: out[0] = v.y, out[1] = (D_b v).v (launch_lmax_step's order and
 // trees), then v <- D_b^-1 y in a pass of its own. partials holds 2 np doubles.
 void launch_lmax_step_block(const pamg_mat& A, const double* y, double* v, double* partials, int np, double* out,

@@ -355,10 +355,12 @@ int apply(pamg_ctx* ctx, const pamg_mat* A, int op, double* x, const double* b, 
     if (op != pamg::OP_CHEB) xold = x;
     else if (A->interior.pnc || A->interior.rpat || (!A->d_diag && A->nrows > 0))
         return fail(PAMG_E_ARG, "chebyshev: a square operator with a nonzero diagonal is needed");
+    if (op == pamg::OP_JACOBI && !A->d_diag && A->nrows > 0)
+        return fail(PAMG_E_ARG, "jacobi: a square operator with a nonzero diagonal is needed");
     hipStream_t s = ctx->s_comp;
     return overlap_exchange(
-        ctx, A->plan, x, [&]() { pamg::launch_rows(*A, A->interior, op, x, b, xold, y, omega, s, c1); },
-        [&]() { pamg::launch_rows(*A, A->boundary, op, x, b, xold, y, omega, s, c1); });
+        ctx, A->plan, x, [&]() { pamg::launch_set(*A, A->interior, op, x, b, xold, y, omega, s, c1); },
+        [&]() { pamg::launch_set(*A, A->boundary, op, x, b, xold, y, omega, s, c1); });
 }
 
 // One smoothing step in point-block form (SPEC §S12) on an operator that carries block data: the residual
@@ -1483,6 +1485,9 @@ int pamg_jacobi(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pamg_vec* b
     if (!ctx || !A || !x || !b || !tmp || nsweeps < 0) return fail(PAMG_E_ARG, "jacobi: bad args");
     CHECK(check_vec_for(A, x, "jacobi"));
     CHECK(check_vec_for(A, tmp, "jacobi"));
+    if (pamg::bsr_any(*A) && A->nrows != (A->plan ? A->plan->n_own : A->ncols))
+        return fail(PAMG_E_ARG, "jacobi: the block-row operator must be square (%lld rows, %lld own columns)",
+                    (long long)A->nrows, (long long)(A->plan ? A->plan->n_own : A->ncols));
     if (!A->d_diag) return fail(PAMG_E_SETUP, "jacobi: matrix is not square or lacks a nonzero diagonal");
     if (b->n_own != A->nrows || tmp == x) return fail(PAMG_E_ARG, "jacobi: size mismatch or aliasing");
     CHECK(set_device(ctx));
@@ -1503,6 +1508,9 @@ int pamg_jacobi_residual(pamg_ctx* ctx, const pamg_mat* A, pamg_vec* x, const pa
     if (!ctx || !A || !x || !b || !t || !r) return fail(PAMG_E_ARG, "jacobi_residual: NULL");
     CHECK(check_vec_for(A, x, "jacobi_residual"));
     CHECK(check_vec_for(A, t, "jacobi_residual"));
+    if (pamg::bsr_any(*A) && A->nrows != (A->plan ? A->plan->n_own : A->ncols))
+        return fail(PAMG_E_ARG, "jacobi_residual: the block-row operator must be square (%lld rows, %lld own columns)",
+                    (long long)A->nrows, (long long)(A->plan ? A->plan->n_own : A->ncols));
     if (!A->d_diag) return fail(PAMG_E_SETUP, "jacobi_residual: matrix is not square or lacks a nonzero diagonal");
     if (b->n_own != A->nrows || r->n_own != A->nrows || t == x || r == x || r == t || b == t || b == r)
         return fail(PAMG_E_ARG, "jacobi_residual: size mismatch or aliasing");
@@ -2622,8 +2630,8 @@ int pamg_bench_rowop(pamg_ctx* ctx, const pamg_mat* A, int op, pamg_vec* x, cons
             if (op >= 4) {
                 pamg::launch_sym_tb(*A, ta, s);
             } else {
-                pamg::launch_rows(*A, A->interior, op, x->d, bd, x->d, y->d, omega, s);
-                pamg::launch_rows(*A, A->boundary, op, x->d, bd, x->d, y->d, omega, s);
+                pamg::launch_set(*A, A->interior, op, x->d, bd, x->d, y->d, omega, s);
+                pamg::launch_set(*A, A->boundary, op, x->d, bd, x->d, y->d, omega, s);
             }
             return (int)PAMG_OK;
         });
@@ -2665,10 +2673,10 @@ Cols subset(const Cols& c, const int* at, int m) {
 // y_c = op(A, x_c[, b_c]) for k columns: apply's bits per column
 int apply_multi(pamg_ctx* ctx, const pamg_mat* A, int op, int k, const Cols& x, const Cols* b, const Cols& y,
                 double omega, double c1 = 0.0, const Cols* xold = nullptr) {
-    if (k > 1 && A->interior.bsr) {
+    if (k > 1 && pamg::bsr_any(*A)) {
         // (a block-row operator has no ghost column: nothing to exchange)
-        if (op == pamg::OP_CHEB && !A->d_diag && A->nrows > 0)
-            return fail(PAMG_E_ARG, "chebyshev: a square operator with a nonzero diagonal is needed");
+        if ((op == pamg::OP_CHEB || op == pamg::OP_JACOBI) && !A->d_diag && A->nrows > 0)
+            return fail(PAMG_E_ARG, "jacobi / chebyshev: a square operator with a nonzero diagonal is needed");
         pamg::launch_bsr_multi(*A, op, 0, k, x.p, b ? b->p : nullptr, xold ? xold->p : nullptr, y.p, omega, c1,
                                ctx->s_comp);
         HIPC(hipGetLastError());

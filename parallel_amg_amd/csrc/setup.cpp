@@ -654,4 +654,102 @@ int pamg_setup_block_diag(const pamg_hcsr* A, int64_t row0, int bs, double* bloc
     return PAMG_OK;
 }
 
+// SPEC §S14: the node matrix N of a node-blocked operator — per stored block (m, c) its Frobenius norm, the
+// squares summed from +0.0 with d outer and e inner, each square and each add rounded once, then one sqrt.
+int pamg_setup_node_matrix(const pamg_hcsr* A, int64_t row0, int bs, pamg_hcsr** out) {
+    if (!valid(A) || !out) return fail(PAMG_E_ARG, "node_matrix: bad args");
+    if (bs < 2 || bs > 4) return fail(PAMG_E_ARG, "node_matrix: block size %d outside 2..4", bs);
+    if (A->nr % bs != 0 || row0 < 0 || row0 % bs != 0)
+        return fail(PAMG_E_ARG, "node_matrix: %lld rows from row %lld are not whole blocks of %d", (long long)A->nr,
+                    (long long)row0, bs);
+    const int64_t nb = A->nr / bs, m0 = row0 / bs;
+    // the node-blocked property: the first node that breaks it (smallest id: a min over independent nodes)
+    int64_t bad = nb;
+#pragma omp parallel for schedule(static) reduction(min : bad)
+    for (int64_t m = 0; m < nb; ++m) {
+        const int64_t k0 = A->rp[m * bs], len = A->rp[m * bs + 1] - k0;
+        bool good = len % bs == 0, has_diag = false;
+        for (int d = 0; d < bs && good; ++d) good = A->rp[m * bs + d + 1] - A->rp[m * bs + d] == len;
+        for (int64_t j = 0; j < len && good; j += bs) {
+            const int64_t c0 = A->col[k0 + j];
+            good = c0 % bs == 0 && (j == 0 || c0 > A->col[k0 + j - bs]);
+            for (int d = 0; d < bs && good; ++d)
+                for (int e = 0; e < bs && good; ++e) good = A->col[A->rp[m * bs + d] + j + e] == c0 + e;
+            has_diag |= c0 == (m0 + m) * bs;
+        }
+        if (!(good && has_diag) && m < bad) bad = m;
+    }
+    if (bad < nb)
+        return fail(PAMG_E_ARG, "node_matrix: node %lld (rows %lld..%lld) is not node-blocked: its %d rows must store "
+                    "the same whole blocks, columns ascending, the diagonal block among them",
+                    (long long)(m0 + bad), (long long)(row0 + bad * bs), (long long)(row0 + bad * bs + bs - 1), bs);
+    try {
+        auto N = std::make_unique<pamg_hcsr>();
+        N->nr = nb;
+        N->nc = (A->nc + bs - 1) / bs;
+        N->rp.assign(nb + 1, 0);
+        for (int64_t m = 0; m < nb; ++m) N->rp[m + 1] = N->rp[m] + (A->rp[m * bs + 1] - A->rp[m * bs]) / bs;
+        N->col.resize(N->rp[nb]);
+        N->val.resize(N->rp[nb]);
+        int64_t zero = nb;
+#pragma omp parallel for schedule(static) reduction(min : zero)
+        for (int64_t m = 0; m < nb; ++m) {
+            const int64_t nblk = N->rp[m + 1] - N->rp[m];
+            for (int64_t k = 0; k < nblk; ++k) {
+                double s = 0.0;
+                for (int d = 0; d < bs; ++d)
+                    for (int e = 0; e < bs; ++e) {
+                        const double a = A->val[A->rp[m * bs + d] + k * bs + e];
+                        const double q = a * a;
+                        s = s + q;
+                    }
+                const int64_t c = A->col[A->rp[m * bs] + k * bs] / bs;
+                N->col[N->rp[m] + k] = (int32_t)c;
+                N->val[N->rp[m] + k] = std::sqrt(s);
+                if (c == m0 + m && s == 0.0 && m < zero) zero = m;
+            }
+        }
+        if (zero < nb)
+            return fail(PAMG_E_SETUP, "node_matrix: the diagonal block of node %lld (rows %lld..%lld) is zero",
+                        (long long)(m0 + zero), (long long)(row0 + zero * bs), (long long)(row0 + zero * bs + bs - 1));
+        *out = N.release();
+    } catch (...) {
+        return fail(PAMG_E_NOMEM, "node_matrix: out of host memory");
+    }
+    return PAMG_OK;
+}
+
+// SPEC §S14: the tentative prolongator of node aggregates, one entry per row in its own unknown's column.
+int pamg_setup_tentative_nodal(int64_t nb, const int32_t* agg, int64_t n_agg, int64_t coarse0_nodes,
+                               int64_t ncols_global, int bs, pamg_hcsr** out) {
+    if ((!agg && nb > 0) || !out || nb < 0 || n_agg < 0 || coarse0_nodes < 0)
+        return fail(PAMG_E_ARG, "tentative_nodal: bad args");
+    if (bs < 2 || bs > 4) return fail(PAMG_E_ARG, "tentative_nodal: block size %d outside 2..4", bs);
+    if (ncols_global % bs != 0 || ncols_global >= (int64_t)INT32_MAX)
+        return fail(PAMG_E_ARG, "tentative_nodal: %lld columns are not whole blocks of %d below 2^31",
+                    (long long)ncols_global, bs);
+    std::vector<int64_t> cnt(n_agg, 0);
+    for (int64_t m = 0; m < nb; ++m)
+        if (agg[m] >= 0) {
+            if (agg[m] >= n_agg || (coarse0_nodes + agg[m] + 1) * bs > ncols_global)
+                return fail(PAMG_E_ARG, "tentative_nodal: aggregate id out of range");
+            cnt[agg[m]]++;
+        }
+    auto T = std::make_unique<pamg_hcsr>();
+    T->nr = nb * bs;
+    T->nc = ncols_global;
+    T->rp.resize(nb * bs + 1);
+    T->rp[0] = 0;
+    for (int64_t m = 0; m < nb; ++m)
+        for (int d = 0; d < bs; ++d) {
+            if (agg[m] >= 0) {
+                T->col.push_back((int32_t)((coarse0_nodes + agg[m]) * bs + d));
+                T->val.push_back(1.0 / std::sqrt((double)cnt[agg[m]]));
+            }
+            T->rp[m * bs + d + 1] = (int64_t)T->col.size();
+        }
+    *out = T.release();
+    return PAMG_OK;
+}
+
 }  // extern "C"

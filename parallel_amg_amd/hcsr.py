@@ -153,6 +153,24 @@ def tentative(agg: np.ndarray, n_agg: int, coarse0: int, ncols_global: int) -> H
     return HCSR(h)
 
 
+def node_matrix(A: HCSR, row0: int, bs: int) -> HCSR:
+    """The node matrix N of a node-blocked operator's own rows (global rows row0..; SPEC §S14): one entry
+    per stored bs x bs block, its Frobenius norm; rows = own nodes, columns = global node ids."""
+    h = C.c_void_p()
+    call("pamg_setup_node_matrix", A.handle, int(row0), int(bs), C.byref(h))
+    return HCSR(h)
+
+
+def tentative_nodal(agg: np.ndarray, n_agg: int, coarse0_nodes: int, ncols_global: int, bs: int) -> HCSR:
+    """Tentative prolongator of node aggregates (SPEC §S14): ``agg`` holds one local aggregate id per own
+    node (-1 isolated); row bs m + d gets the entry (bs (coarse0_nodes + agg[m]) + d, 1/sqrt(|agg|))."""
+    h = C.c_void_p()
+    agg = np.ascontiguousarray(agg, np.int32)
+    call("pamg_setup_tentative_nodal", len(agg), ptr(agg), n_agg, int(coarse0_nodes), int(ncols_global),
+         int(bs), C.byref(h))
+    return HCSR(h)
+
+
 def spgemm(X: HCSR, y0: int, Yown: HCSR, ghost_ids=None, Yghost: HCSR | None = None,
            device=None) -> HCSR:
     """C = X * Y (SPEC §S4.5). ``device``: a partitioned.Context -> the GPU routine

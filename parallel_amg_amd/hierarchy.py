@@ -27,6 +27,9 @@ class SAParams:
     # SPEC §S7 agglomeration: levels >= 1 with <= this many global rows are built as one part
     # and replicated on every part; 0 = decoupled on every level
     agglomerate: int = 32768
+    # SPEC §S14 nodal aggregation: > 1 (2..4) aggregates the nodes of a node-blocked operator, rows
+    # block_size * m + d, so that every A_l, P_l and R_l keeps whole blocks; 1 = scalar aggregation (§S4)
+    block_size: int = 1
 
 
 @dataclass
@@ -126,7 +129,7 @@ class LevelPart:
     omega: float
     rho: float
     planA: HostPlan = None
-    agg: np.ndarray = None          # local aggregate ids (-1 isolated)
+    agg: np.ndarray = None          # local aggregate ids (-1 isolated); of nodes in a nodal hierarchy (§S14)
     P: HCSR = None                  # own fine rows x global coarse cols
     R: HCSR = None                  # own coarse rows (next level) x global fine cols
     planP: HostPlan = None          # column space: next level
@@ -145,6 +148,7 @@ class HostHierarchy:
     # and how the restriction into it distributes its rows over the parts
     rep_level: int = 0
     rep_offsets: np.ndarray = None
+    block_size: int = 1     # SPEC §S14: > 1 for a nodal hierarchy (every A_l, P_l and R_l node-blocked)
 
     @property
     def nlevels(self):
@@ -302,10 +306,20 @@ def build_hierarchy(backend, A: dict, offsets: np.ndarray, params: SAParams = SA
 
     ``device`` (a partitioned.Context): the Galerkin products (A T, A P, R (A P)) and the
     transposes run on that GPU (spgemm.hip, SURVEY §8f-4) — bit-identical to the host routines;
-    strength, aggregation and the coarsest inverse stay on the host (§8f-4)."""
+    strength, aggregation and the coarsest inverse stay on the host (§8f-4).
+
+    ``params.block_size`` > 1 takes SPEC §S14's path on every level: A is node-blocked (rows
+    ``bs m + d``), the nodes are aggregated through the node matrix, and every A_l, P_l and R_l is
+    node-blocked again. ValueError where a part offset is not a multiple of the block size."""
     dv = device
     parts = backend.parts
     offs = np.asarray(offsets, np.int64)
+    bs = int(params.block_size)
+    if bs != 1:
+        if not 2 <= bs <= 4:
+            raise ValueError(f"build_hierarchy: block_size {bs} outside 1..4")
+        if np.any(offs % bs):
+            raise ValueError(f"build_hierarchy: part offsets {offs.tolist()} are not multiples of block_size {bs}")
     levels = []
     while True:
         n = int(offs[-1])
@@ -320,14 +334,22 @@ def build_hierarchy(backend, A: dict, offsets: np.ndarray, params: SAParams = SA
         levels.append(lev)
         if n <= params.max_coarse or len(levels) >= params.max_levels:
             break
-        aggs = {p: H.aggregate(A[p], int(offs[p]), params.theta) for p in parts}
+        if bs == 1:
+            aggs = {p: H.aggregate(A[p], int(offs[p]), params.theta) for p in parts}
+        else:  # §S14: §S4.2-3 unchanged on the node matrix; agg holds node aggregates
+            aggs = {p: H.aggregate(H.node_matrix(A[p], int(offs[p]), bs), int(offs[p]) // bs, params.theta)
+                    for p in parts}
         nagg = backend.allgather({p: aggs[p][1] for p in parts})
         coffs = np.zeros(backend.nparts + 1, np.int64)
         np.cumsum(nagg, out=coffs[1:])
+        coffs *= bs
         nc = int(coffs[-1])
         if nc == 0 or nc >= n:
             break
-        T = {p: H.tentative(aggs[p][0], aggs[p][1], int(coffs[p]), nc) for p in parts}
+        if bs == 1:
+            T = {p: H.tentative(aggs[p][0], aggs[p][1], int(coffs[p]), nc) for p in parts}
+        else:
+            T = {p: H.tentative_nodal(aggs[p][0], aggs[p][1], int(coffs[p]) // bs, nc, bs) for p in parts}
         Tg = fetch_rows(backend, planA, T)
         P = {}
         for p in parts:
@@ -386,7 +408,7 @@ def build_hierarchy(backend, A: dict, offsets: np.ndarray, params: SAParams = SA
         full = _gather_full(backend, {p: last[p].A for p in parts}, offs)
     ainv = H.cholinv(full)
     return HostHierarchy(backend.nparts, parts, levels, ainv, int(offs[-1]),
-                         rep_level=len(levels) - 1, rep_offsets=offs)
+                         rep_level=len(levels) - 1, rep_offsets=offs, block_size=bs)
 
 
 def _replicated_tail(backend, A: dict, offs, levels: list, params: SAParams, log, device):
@@ -413,7 +435,8 @@ def _replicated_tail(backend, A: dict, offs, levels: list, params: SAParams, log
         lp.whole = True
         levels.append({p: lp for p in backend.parts})
     return HostHierarchy(backend.nparts, backend.parts, levels, sub.ainv, sub.n_coarse,
-                         rep_level=len(levels) - sub.nlevels, rep_offsets=np.asarray(offs, np.int64))
+                         rep_level=len(levels) - sub.nlevels, rep_offsets=np.asarray(offs, np.int64),
+                         block_size=sub.block_size)
 
 
 def _gather_full(backend, A: dict, offs) -> HCSR:

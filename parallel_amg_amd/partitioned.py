@@ -405,7 +405,7 @@ class PSparseMatrix:
 
     def __init__(self, ctx: Context, M: HCSR, plan: HostPlan | None = None,
                  dplan: DevicePlan | None = None, row_perm=None, col_perm=None, tag: int = 0,
-                 block_size: int = 1):
+                 block_size: int = 1, block_rows: int = 1):
         """``row_perm`` / ``col_perm`` (pamg_mat_upload_perm): device row i is row
         ``row_perm[i]`` of M, device own column k is own column ``col_perm[k]`` (None: the
         identity); rows keep their storage order, so row sums keep their bits. ``tag``: the
@@ -413,9 +413,14 @@ class PSparseMatrix:
         square node-major operator of that many unknowns per node; where every node's rows store the
         same whole blocks and no row has a ghost column it takes the block-row layout
         (``self.blocked``; same bits), otherwise the layouts of a plain upload. Not with a
-        permutation: renumber the nodes before setup."""
-        block_size = int(block_size)
-        if block_size > 1 and (row_perm is not None or col_perm is not None):
+        permutation: renumber the nodes before setup. ``block_rows`` > 1
+        (pamg_mat_upload_block_rows): the same for an operator that may be rectangular, between two
+        node-major spaces of that block size (the P and R of a nodal hierarchy, SPEC §S14); no diagonal is
+        asked for and ``self.blocked`` tells whether the block-row layout was taken."""
+        block_size, block_rows = int(block_size), int(block_rows)
+        if block_size != 1 and block_rows != 1:
+            raise ValueError("PSparseMatrix: give block_size (square operators) or block_rows, not both")
+        if (block_size > 1 or block_rows > 1) and (row_perm is not None or col_perm is not None):
             raise ValueError("PSparseMatrix: block_size > 1 cannot be combined with row_perm / col_perm "
                              "(the block-row layout has no permuted variant: renumber the nodes before setup)")
         self.ctx = ctx
@@ -432,6 +437,9 @@ class PSparseMatrix:
         if block_size != 1:
             call("pamg_mat_upload_blocked", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
                  ptr(M.val), 0, dplan.handle if dplan is not None else None, block_size, C.byref(h))
+        elif block_rows != 1:
+            call("pamg_mat_upload_block_rows", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
+                 ptr(M.val), 0, dplan.handle if dplan is not None else None, block_rows, C.byref(h))
         elif row_perm is None and col_perm is None:
             call("pamg_mat_upload", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
                  ptr(M.val), 0, dplan.handle if dplan is not None else None, C.byref(h))
@@ -451,10 +459,12 @@ class PSparseMatrix:
         self.stream_bytes = sb.value  # matrix bytes one row operation reads (uploaded layout)
         self.block_size = 1
         self.blocked = False  # the rows run in the block-row layout (pamg_mat_layout bit 15)
-        if block_size != 1:
+        self.row_lanes = False
+        if block_size != 1 or block_rows != 1:
             lay = (C.c_int * 10)()
             call("pamg_mat_layout", h, 0, lay)
             self.blocked = bool(lay[9] & 32768)
+            self.row_lanes = self.blocked and lay[6] == 1  # its row-per-lane form (k_rows_bsr_r)
 
     def set_block_diag(self, bs: int = 1, blocks=None, inv=None):
         """Attach the point blocks of the own rows and their inverses (``hcsr.block_diag``'s arrays;

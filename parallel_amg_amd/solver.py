@@ -65,6 +65,13 @@ class AMGSolver:
         four distinct values fit the dictionary tiles, which stream a seventh of the bytes (18.3 ms
         against 37.8 with the block-row layout).
 
+        On a nodal hierarchy (``SAParams(block_size=bs)``, SPEC §S14) every level keeps node structure:
+        ``block_layout="all"`` uploads every A_l through pamg_mat_upload_blocked and every P_l and R_l
+        through pamg_mat_upload_block_rows with the hierarchy's block size (ValueError on a hierarchy
+        built with ``block_size=1``); ``{"A": {...}, "P": {...}, "R": {...}}`` names the levels of each
+        (``{level: block size}``, as above). The multi-column cycle then streams every operator once per
+        chunk of columns. Which to take: DESIGN.md, "Nodal hierarchy".
+
         ``reorder`` (one part only): a locality permutation of every level but the coarsest
         inside the device layout (pamg_locality_order / pamg_mat_upload_perm): "auto" takes
         reverse Cuthill-McKee on the levels whose numbering is scattered (FE meshes, random
@@ -107,18 +114,38 @@ class AMGSolver:
                 order, before, after = locality_order(H.levels[l][part].A, mode)
                 self.perm[l] = order
                 self.span[l] = (round(before, 1), round(after, 1))
+        transfers = {"P": {}, "R": {}}
+        if isinstance(block_layout, str):
+            if block_layout != "all":
+                raise ValueError(f"block_layout: {block_layout!r} (a block size, a dict or 'all')")
+            hbs = int(getattr(H, "block_size", 1))
+            if hbs == 1:
+                raise ValueError("block_layout='all' needs a nodal hierarchy (SAParams(block_size=bs), SPEC §S14): "
+                                 "this one was built with block_size=1")
+            block_layout = {l: hbs for l in range(H.nlevels)}
+            transfers = {w: {l: hbs for l in range(H.nlevels - 1)} for w in ("P", "R")}
+        elif isinstance(block_layout, dict) and any(isinstance(k, str) for k in block_layout):
+            if set(block_layout) - {"A", "P", "R"}:
+                raise ValueError(f"block_layout: keys {sorted(map(str, block_layout))} (levels, or 'A', 'P' and 'R')")
+            transfers = {w: dict(block_layout.get(w) or {}) for w in ("P", "R")}
+            block_layout = dict(block_layout.get("A") or {})
         if block_layout is None:
             block_layout = {}
         elif not isinstance(block_layout, dict):
             block_layout = {0: block_layout}
         self.block_layout = {range(H.nlevels)[int(l)]: int(bs) for l, bs in block_layout.items() if int(bs) != 1}
-        for l, bs in self.block_layout.items():
-            if bs < 1 or bs > 4:
-                raise ValueError(f"block_layout: block size {bs} of level {l} outside 1..4")
-            if self.perm[l] is not None:
-                raise ValueError(f"block_layout: level {l} is uploaded with a locality permutation, which the "
-                                 "block-row layout does not take (build the solver with reorder='off' and "
-                                 "renumber the nodes before setup)")
+        # the transfers in the block-row layout (pamg_mat_upload_block_rows): level -> block size
+        self.block_layout_P, self.block_layout_R = (
+            {range(H.nlevels - 1)[int(l)]: int(bs) for l, bs in transfers[w].items() if int(bs) != 1}
+            for w in ("P", "R"))
+        for which, lay in (("A", self.block_layout), ("P", self.block_layout_P), ("R", self.block_layout_R)):
+            for l, bs in lay.items():
+                if bs < 1 or bs > 4:
+                    raise ValueError(f"block_layout: block size {bs} of level {l} outside 1..4")
+                if self.perm[l] is not None or (which != "A" and self.perm[l + 1] is not None):
+                    raise ValueError(f"block_layout: level {l} is uploaded with a locality permutation, which the "
+                                     "block-row layout does not take (build the solver with reorder='off' and "
+                                     "renumber the nodes before setup)")
         for l in range(H.nlevels):
             lp = H.levels[l][part]
             pl = self.perm[l]
@@ -129,8 +156,10 @@ class AMGSolver:
             self.omega.append(lp.omega)
             if l < H.nlevels - 1:
                 self.P.append(PSparseMatrix(ctx, lp.P, None if l + 1 >= rep else lp.planP,
-                                            row_perm=pl, col_perm=pn, tag=plan_tag(l, "P")))
-                self.R.append(PSparseMatrix(ctx, lp.R, lp.planR, row_perm=pn, col_perm=pl, tag=plan_tag(l, "R")))
+                                            row_perm=pl, col_perm=pn, tag=plan_tag(l, "P"),
+                                            block_rows=self.block_layout_P.get(l, 1)))
+                self.R.append(PSparseMatrix(ctx, lp.R, lp.planR, row_perm=pn, col_perm=pl, tag=plan_tag(l, "R"),
+                                            block_rows=self.block_layout_R.get(l, 1)))
         self.level_rows = [int(H.levels[l][part].A.nrows) for l in range(H.nlevels)]
         self.n_coarse = H.n_coarse
         L = self.L
@@ -195,12 +224,17 @@ class AMGSolver:
         """Attach point-block data of ``bs`` unknowns per node (2..4; SPEC §S12) to the operators of
         ``levels`` — row ``bs m + d`` is unknown d of node m — for the "block_jacobi" and
         "block_chebyshev" smoothers; ``bs = 1`` removes it. The default is level 0 alone: scalar-strength
-        aggregation mixes a node's unknowns, so coarser levels have no node structure. Raises
+        aggregation mixes a node's unknowns, so coarser levels have no node structure. On a nodal
+        hierarchy (SPEC §S14) every level has: ``levels="all"`` names every level but the coarsest. Raises
         ValueError for a level whose device layout is permuted (``reorder``) or whose part offsets are
         not multiples of ``bs``. ``self.rho_b[l]`` keeps ||D_b^-1 A_l||_inf, the maximum over the parts
         this process holds, or over all of them through ``backend.allreduce_max``. Call
         ``set_smoother`` afterwards."""
         bs = int(bs)
+        if isinstance(levels, str):
+            if levels != "all":
+                raise ValueError(f"set_block_size: levels {levels!r} (level numbers or 'all')")
+            levels = range(self.L - 1)
         for l in levels:
             l = range(self.L - 1)[l]
             A = self.A_dev[l]
