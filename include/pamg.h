@@ -247,7 +247,8 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes);
  * grid); bit 12: with bit 10, the rows hold 16-bit combination ids instead of 64-bit records
  * (pnc_compact; out[4] = the combinations); bit 13: with bit 9, one index byte per nonzero names an
  * (offset, value) pair of the group (ell_pair); bit 14: with bit 10, the grid cuts into whole tiles
- * and "pnc" = 1 launches the tiled march (k_rows_pnct) for it (out[8] is the grid of either march);
+ * and "pnc" = 1 launches the tiled march with the coarse values staged in LDS (k_rows_pncv) for it, "pnc" = 3
+ * the one with the anchors staged (k_rows_pnct), "pnc" = 2 the line-block march (out[8] is the grid of all three);
  * bit 15: the set runs in the block-row layout (bsr; pamg_mat_upload_blocked, pamg_mat_upload_block_rows:
  * then out[3] = the block size, out[4] = the padded block slots, out[8] = the kernel's grid, and out[6] = 1
  * where a restriction-shaped operator took the row-per-lane form — a lane per scalar row, the slots per

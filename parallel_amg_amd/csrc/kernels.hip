@@ -2437,6 +2437,209 @@ __global__ __launch_bounds__(256) void k_rows_pnct(int nrows, int nx, int M, int
     }
 }
 
+// a stream's march state in k_rows_pncv: the row's record and y / b, the coarse values E of the
+// points i - M, i, i + M, the anchor of the point two planes on, and (a tile's edge threads) the
+// next plane's E and the anchor two planes on of their ring point
+struct PncvRow {
+    uint2 rec;   // as PncRow::rec
+    double p0;
+    double em, e0, ep;
+    int a2;
+    double gp;
+    int ga2;
+};
+
+// k_rows_pncv: k_rows_pnct's march with the coarse values in LDS instead of the anchors. Every
+// column of row i is the anchor of one of the 7 points i, i +- 1, i +- nx, i +- M (pamg_device.h),
+// so every x[column] a row takes is E(p) = x[anc[p]] at its own point or a grid neighbour: a lane
+// gathers E of its own point once per plane — for the plane two on, from the anchor it loaded a
+// step before; the anchor three planes on is loaded under it — keeps its z neighbours' E in
+// registers (em, e0, ep) and takes the in-plane neighbours' from the stream's LDS plane
+// ((TX + 2) x (TY + 2) doubles, two buffers: the next plane is written while this one is read, one
+// barrier per step). The tile's edge threads gather E of their ring point as well (off the grid:
+// the edge row's own; no code names such a point). One gather per row and plane plus the ring's
+// share instead of one per entry, none behind an LDS read, and no switch over the gather count.
+// The gather is unconditional: build_pnc sets anc[p] to a column of row p for every row of the
+// grid — rows outside the set (several parts: the boundary rows, whose anchor may be a ghost slot
+// the exchange has not filled yet) included — and to 0 for an empty row, so x[anc[p]] is always
+// inside x; no row of the set names a point whose anchor is a ghost slot, and an entry's value is
+// picked by an address and selects, never by arithmetic, so such an E reaches no sum.
+// The step is bound by its vector instructions, not its loads (a select chain over doubles for all
+// 7 entries: 216 per row, 1.03 ms at 512^3 against the anchors' 0.91), so the codes are decoded
+// once per workgroup, not per row: a pattern (CP: combination) becomes 7 signed bytes, entry k's
+// offset from the lane's place in the LDS plane, and its row length; entry k is one LDS read at
+// that offset — or em / ep where the byte names a z neighbour — and entries past the row's length
+// are skipped under the exec mask, which also ends a wave's entries at its longest row. The
+// products, their order and the left-to-right sum from +0.0 are k_rows_pnct's (SPEC S3): the same
+// bits. The tables sit in dynamic LDS sized by the operator (nval doubles, then with CP npat
+// 64-bit value-index words, then npat offset words of 8 B): 20.5 KB a workgroup with the planes
+// at the 512^3 P0 (428 combinations, 63 VGPRs). TX x TY threads: one row per lane.
+// No OP_JACOBI: it needs the columns (prolongations are not square; the API refuses it before).
+template <int OP, int NS, bool CP, int TX, int TY>
+__global__ __launch_bounds__(TX * TY) void k_rows_pncv(int nrows, int nx, int M, int nz, int zlen,
+                                                       const int* __restrict__ anc, const uint2* __restrict__ rec,
+                                                       const uint16_t* __restrict__ cid, const uint64_t* __restrict__ pvals,
+                                                       const uint32_t* __restrict__ ptab, int npat,
+                                                       const double* __restrict__ vtab, int nval,
+                                                       const double* __restrict__ x, const double* __restrict__ b,
+                                                       double* __restrict__ y, double omega) {
+    constexpr int NT = TX * TY, LW = TX + 2, LP = LW * (TY + 2);
+    static_assert(OP != OP_JACOBI, "the diagonal test needs the columns: k_rows_pnct");
+    static_assert(NT % 64 == 0 && NT <= 1024 && 2 * TX + 2 * TY <= NT, "one row per lane; one ring point per edge thread");
+    __shared__ double le[NS][2][LP];
+    extern __shared__ double pncv_tab[];
+    double* lv = pncv_tab;  // (pncv_lds_bytes: at least one value, the index of an entry past a row's length)
+    uint64_t* lw = reinterpret_cast<uint64_t*>(pncv_tab + max(nval, 1));
+    uint2* lo = reinterpret_cast<uint2*>(lw + (CP ? npat : 0));
+    static_assert(LW > 2 && LW < 128, "a pattern's LDS offsets are signed bytes; +-2 name the z neighbours");
+    const int nxb = M / NT;                                    // tiles of a plane
+    const int units = nxb * ((nz + zlen - 1) / zlen);
+    const int per = (units + 7) >> 3;
+    const int u = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);  // consecutive units on one XCD
+    if (u >= units) return;  // the whole workgroup, before the barrier
+    const int tid = (int)threadIdx.x;
+    // a pattern word decoded once per workgroup: entry k's code as the offset, in doubles, from the
+    // lane's place in the LDS plane (a signed byte: 0, -1, 1, -LW, LW; 2 and -2 — inside the plane,
+    // named by no code — stand for i - M and i + M, which the lane holds); the row length in bits 56..
+    for (int t = tid; t < npat; t += NT) {
+        const uint32_t w = ptab[t];
+        uint32_t o[2] = {0u, (w & 7u) << 24};
+#pragma unroll
+        for (int k = 0; k < kPncMaxLen; ++k) {
+            const uint32_t c = (w >> (3 + 3 * k)) & 7u;
+            const int e = c == 1u ? -1 : c == 2u ? 1 : c == 3u ? -LW : c == 4u ? LW : c == 5u ? 2 : c == 6u ? -2 : 0;
+            o[k >> 2] |= ((uint32_t)e & 255u) << (8 * (k & 3));
+        }
+        lo[t] = make_uint2(o[0], o[1]);
+    }
+    if constexpr (CP)
+        for (int t = tid; t < npat; t += NT) lw[t] = pvals[t];
+    for (int t = tid; t < nval; t += NT) lv[t] = vtab[t];
+    const int zc0 = (u / nxb) * zlen, zc1 = min(nz, zc0 + zlen);
+    const int part = (zc1 - zc0 + NS - 1) / NS;  // planes per stream
+    const int tpx = nx / TX, ny = M / nx, tb = u % nxb;
+    const int x0 = (tb % tpx) * TX, y0 = (tb / tpx) * TY;
+    const int ixy = (y0 + tid / TX) * nx + x0 + tid % TX;
+    const int lpos = (tid / TX + 1) * LW + tid % TX + 1;
+    // the ring: threads 0 .. 2 TX - 1 the lines below and above the tile, the last 2 TY threads the
+    // points left and right of it (rxy: the point in its plane, clamped to the tile's edge off the grid)
+    int rxy = -1, rpos = 0;
+    if (tid < TX) {
+        rxy = (y0 > 0 ? y0 - 1 : y0) * nx + x0 + tid;
+        rpos = tid + 1;
+    } else if (tid < 2 * TX) {
+        rxy = (y0 + TY < ny ? y0 + TY : y0 + TY - 1) * nx + x0 + tid - TX;
+        rpos = (TY + 1) * LW + tid - TX + 1;
+    } else if (tid >= NT - TY) {
+        rxy = (y0 + tid - (NT - TY)) * nx + (x0 + TX < nx ? x0 + TX : x0 + TX - 1);
+        rpos = (tid - (NT - TY) + 1) * LW + TX + 1;
+    } else if (tid >= NT - 2 * TY) {
+        rxy = (y0 + tid - (NT - 2 * TY)) * nx + (x0 > 0 ? x0 - 1 : x0);
+        rpos = (tid - (NT - 2 * TY) + 1) * LW;
+    }
+    int zs[NS], ze[NS], zl[NS], za[NS];
+    PncvRow r[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        zs[q] = zc0 + q * part;
+        ze[q] = min(zc1, zs[q] + part);
+        zl[q] = ze[q] > zs[q] ? ze[q] - 1 : zc1 - 1;  // a stream's last plane (an empty stream re-walks the chunk's)
+        // za: the plane of r.e0 — the row's plane until the stream's last, then on to the grid's last
+        // (steps that store nothing: any plane's E are values of x)
+        const int z = za[q] = min(zs[q], zl[q]), zp = min(z + 1, nz - 1), z2 = min(z + 2, nz - 1), i = z * M + ixy;
+        if constexpr (CP) r[q].rec = make_uint2((uint32_t)cid[i], 0u);
+        else r[q].rec = rec[i];
+        r[q].p0 = 0.0;
+        if constexpr (OP == OP_RESID) r[q].p0 = b[i];
+        if constexpr (OP == OP_PROLONG) r[q].p0 = y[i];
+        r[q].e0 = x[anc[i]];
+        r[q].em = x[anc[z > 0 ? i - M : i]];
+        r[q].ep = x[anc[zp * M + ixy]];
+        r[q].a2 = anc[z2 * M + ixy];
+        r[q].gp = 0.0;
+        r[q].ga2 = 0;
+        le[q][0][lpos] = r[q].e0;
+        if (rxy >= 0) {
+            le[q][0][rpos] = x[anc[z * M + rxy]];
+            r[q].gp = x[anc[zp * M + rxy]];
+            r[q].ga2 = anc[z2 * M + rxy];
+        }
+    }
+    __syncthreads();  // (the tables, the first planes' E)
+    for (int j = 0; j < part; ++j) {
+        uint2 ow[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const uint32_t pid = CP ? r[q].rec.x : r[q].rec.x & 1023u;
+            ow[q] = pid < (uint32_t)npat ? lo[pid] : make_uint2(0u, 0u);  // (kPncSkip / kPncCombSkip: no entries, no store)
+            // the next plane's E into the other buffer
+            le[q][(j & 1) ^ 1][lpos] = r[q].ep;
+            if (rxy >= 0) le[q][(j & 1) ^ 1][rpos] = r[q].gp;
+        }
+        // the next planes (a stream's last plane reloads itself), E two planes on, the anchors three on
+        uint2 nrec[NS];
+        double np0[NS], e2[NS], g2[NS];
+        int a3[NS], ga3[NS];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const int in = min(zs[q] + j + 1, zl[q]) * M + ixy, z3 = min(za[q] + 3, nz - 1);
+            if constexpr (CP) nrec[q] = make_uint2((uint32_t)cid[in], 0u);
+            else nrec[q] = rec[in];
+            np0[q] = 0.0;
+            if constexpr (OP == OP_RESID) np0[q] = b[in];
+            if constexpr (OP == OP_PROLONG) np0[q] = y[in];
+            e2[q] = x[r[q].a2];
+            a3[q] = anc[z3 * M + ixy];
+            g2[q] = 0.0;
+            ga3[q] = 0;
+            if (rxy >= 0) {
+                g2[q] = x[r[q].ga2];
+                ga3[q] = anc[z3 * M + rxy];
+            }
+        }
+        // the sums: an entry past the row's length is selected away
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const int i = min(zs[q] + j, zl[q]) * M + ixy, L = (int)(ow[q].y >> 24);
+            // the value indices from bit 0 (compact: the combination's word; else the record's bits 10..)
+            uint64_t rr;
+            if constexpr (CP) rr = r[q].rec.x < (uint32_t)npat ? lw[r[q].rec.x] : 0ull;
+            else rr = (((uint64_t)r[q].rec.y << 32) | r[q].rec.x) >> 10;
+            const double* pl = &le[q][j & 1][lpos];  // this plane's E at the lane's own point
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < kPncMaxLen; ++k) {
+                // an entry past the row's length is skipped, never masked by arithmetic: a wave leaves the
+                // entries once its longest row is done (512^3 P0: 4.6 of 7 on average)
+                if (k < L) {
+                    const int o = (int)((k < 4 ? ow[q].x : ow[q].y) << (24 - 8 * (k & 3))) >> 24;
+                    const double ei = pl[o];
+                    const double xv = o == 2 ? r[q].em : o == -2 ? r[q].ep : ei;
+                    const double v = lv[(uint32_t)(rr >> (7 * k)) & 127u];
+                    const double p = v * xv;
+                    s = s + p;
+                }
+            }
+            double out;
+            if constexpr (OP == OP_SPMV) out = s;
+            else if constexpr (OP == OP_RESID) out = r[q].p0 - s;
+            else out = r[q].p0 + s;
+            const bool in = CP ? r[q].rec.x != (uint32_t)kPncCombSkip : (r[q].rec.x & 1023u) != (uint32_t)kPncSkip;
+            if (zs[q] + j < ze[q] && in) y[i] = out;
+            r[q].rec = nrec[q];
+            r[q].p0 = np0[q];
+            r[q].em = r[q].e0;
+            r[q].e0 = r[q].ep;
+            r[q].ep = e2[q];
+            r[q].a2 = a3[q];
+            r[q].gp = g2[q];
+            r[q].ga2 = ga3[q];
+            za[q] = min(za[q] + 1, nz - 1);
+        }
+        __syncthreads();  // (the next plane's E written, this plane's read)
+    }
+}
+
 template <int OP>
 __global__ __launch_bounds__(kBlock) void k_rows_long(
     const int* __restrict__ rows, const int* __restrict__ rowptr, const int* __restrict__ col,
@@ -2988,24 +3191,36 @@ void launch_sym(const pamg_mat& A, const double* x, const double* b, double* y, 
 // units and units sized to fill the chip in equal rounds 1.14 / 1.12 / 1.11 ms, against 1.09-1.10)
 constexpr int kPncZlen = 32, kPncStreams = 2;
 
-// Options::pnc read per launch: 1 the tiled march (k_rows_pnct) where the plane cuts into whole
-// kPncTx x kPncTy tiles, 2 (and the other grids) the line-block march (k_rows_pnc). Both take the
-// same units — 256 points of a plane over kPncZlen planes — and so the same grid (PncSet::grid).
+// Options::pnc read per launch, where the plane cuts into whole kPncTx x kPncTy tiles: 1 the tiled
+// march with the coarse values in LDS (k_rows_pncv), 3 the one with the anchors in LDS
+// (k_rows_pnct; OP_JACOBI under 1 too: it needs the columns); 2 (and the other grids) the
+// line-block march (k_rows_pnc). All take the same units — 256 points of a plane over kPncZlen
+// planes — and so the same grid (PncSet::grid). k_rows_pncv's tables: dynamic LDS sized by the
+// operator (the kernel's layout).
 template <int OP>
 void launch_pnc(const pamg_mat& A, const double* x, const double* b, double* y, double omega, hipStream_t s) {
     const PncSet& P = A.pnc;
     const int zlen = std::min(kPncZlen, P.nz);
-    const int nxb = P.nx * P.ny / 256, units = nxb * ((P.nz + zlen - 1) / zlen);
-    auto go = [&](auto kern) {
-        kern<<<(units + 7) / 8 * 8, 256, 0, s>>>((int)A.nrows, P.nx, P.nx * P.ny, P.nz, zlen, P.d_anc, P.d_rec, P.d_cid,
-                                                P.d_pvals, P.d_ptab, P.npat, P.d_vtab, P.nval, x, b, y, omega);
+    const int chunks = (P.nz + zlen - 1) / zlen;
+    auto go = [&](auto kern, int nt, size_t lds) {
+        const int units = P.nx * P.ny / nt * chunks;
+        kern<<<(units + 7) / 8 * 8, nt, lds, s>>>((int)A.nrows, P.nx, P.nx * P.ny, P.nz, zlen, P.d_anc, P.d_rec, P.d_cid,
+                                                 P.d_pvals, P.d_ptab, P.npat, P.d_vtab, P.nval, x, b, y, omega);
     };
-    if (options().pnc == 1 && pnc_tiled(P.nx, P.ny)) {
-        if (P.d_cid) go(k_rows_pnct<OP, kPncStreams, true, kPncTx, kPncTy>);
-        else go(k_rows_pnct<OP, kPncStreams, false, kPncTx, kPncTy>);
+    const size_t tab = sizeof(double) * std::max(P.nval, 1) + (P.d_cid ? 16 : 8) * (size_t)P.npat;
+    const int mode = options().pnc;
+    const bool tiled = pnc_tiled(P.nx, P.ny);
+    if (OP != OP_JACOBI && mode == 1 && tiled) {
+        if constexpr (OP != OP_JACOBI) {
+            if (P.d_cid) go(k_rows_pncv<OP, kPncStreams, true, kPncTx, kPncTy>, kPncTx * kPncTy, tab);
+            else go(k_rows_pncv<OP, kPncStreams, false, kPncTx, kPncTy>, kPncTx * kPncTy, tab);
+        }
+    } else if ((mode == 1 || mode == 3) && tiled) {
+        if (P.d_cid) go(k_rows_pnct<OP, kPncStreams, true, kPncTx, kPncTy>, 256, 0);
+        else go(k_rows_pnct<OP, kPncStreams, false, kPncTx, kPncTy>, 256, 0);
     } else {
-        if (P.d_cid) go(k_rows_pnc<OP, kPncStreams, true>);
-        else go(k_rows_pnc<OP, kPncStreams, false>);
+        if (P.d_cid) go(k_rows_pnc<OP, kPncStreams, true>, 256, 0);
+        else go(k_rows_pnc<OP, kPncStreams, false>, 256, 0);
     }
 }
 

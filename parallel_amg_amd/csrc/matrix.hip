@@ -225,6 +225,14 @@ std::vector<std::array<int64_t, 4>> grids_of(pamg_ctx* ctx) {
     return ctx->grids;
 }
 
+// a 7-point grid operator's grid, for a later prolongation / restriction over it (pnc, ELL group order)
+void register_grid(pamg_ctx* ctx, int64_t n, int64_t nx, int64_t ny, int64_t nz) {
+    const std::array<int64_t, 4> gk{n, nx, ny, nz};
+    std::lock_guard<std::mutex> lk(ctx->grids_mu);
+    auto& gs = ctx->grids;
+    if (std::find(gs.begin(), gs.end(), gk) == gs.end()) gs.push_back(gk);
+}
+
 // A restriction over a registered grid (Options::ell_yblock > 0; its columns are the grid's points):
 // the groups of kEllGroup rows of each XCD's eighth (kernels.hip k_rows_ell / k_rows_rpat) in
 // (y / yblock, z, y) order of their first row's anchor, so the window of groups in flight is a
@@ -528,13 +536,16 @@ int build_sym_dia(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double*
     // 7-point grid stencil in natural order (classes 1, nx, nx*ny; n = nx*ny*nz) whose rows
     // never reach across a grid line (the -1 / +1 / -nx / +nx classes absent at x = 0 / nx-1 /
     // y = 0 / ny-1), tiles of kTbX x kTbY
+    const bool slab = part;  // (a slab of whole planes registers its grid whatever its bands)
     part = part && sd.band == Mp;
-    if (nu == 3 && mb == 1 && (whole || part) && sd.off[0] == 1 && sd.off[2] % sd.off[1] == 0 && n % sd.off[2] == 0) {
+    if (nu == 3 && mb == 1 && (whole || slab) && sd.off[0] == 1 && sd.off[2] % sd.off[1] == 0 && n % sd.off[2] == 0) {
         const int nx = sd.off[1], ny = sd.off[2] / sd.off[1];
         const int nz = (int)(n / sd.off[2]);
-        bool ok = nx % pamg::kTbX == 0 && ny % pamg::kTbY == 0;
+        // (ok: the blocked sweeps' tiles; reg: the grid registers for a later prolongation / restriction —
+        // the neighbour-coded march's tiles, which every kTbX x kTbY grid cuts into as well)
+        const bool ok = nx % pamg::kTbX == 0 && ny % pamg::kTbY == 0, reg = ok || pamg::pnc_tiled(nx, ny);
         std::atomic<bool> cross{false};
-        if (ok)
+        if (reg)
             par_for(n, [&](int64_t a0, int64_t b0) {
                 for (int64_t i = a0; i < b0 && !cross; ++i) {
                     const int x = (int)(i % nx), y = (int)((i / nx) % ny);
@@ -544,7 +555,7 @@ int build_sym_dia(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double*
                         cross = true;
                 }
             });
-        if (ok && !cross) {
+        if (ok && !cross && (whole || part)) {
             pamg::TbGeom& g = sd.tb;
             g.nx = nx;
             g.ny = ny;
@@ -562,14 +573,25 @@ int build_sym_dia(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double*
             g.zhi = nz;
             sd.tb_ok = whole;
             sd.tb_part = part;
-            if (whole || part) {  // (a later prolongation / restriction over this grid: pnc, ELL group order)
-                const std::array<int64_t, 4> gk{n, nx, ny, nz};
-                std::lock_guard<std::mutex> lk(A->ctx->grids_mu);
-                auto& gs = A->ctx->grids;
-                if (std::find(gs.begin(), gs.end(), gk) == gs.end()) gs.push_back(gk);
-            }
             sd.part_lo = part ? plo : 0;
             sd.part_hi = part ? phi : nz;
+        }
+        if (reg && !cross) register_grid(A->ctx, n, nx, ny, nz);
+    } else if (nu == 2 && mb == 1 && whole && sd.off[0] == 1 && n % sd.off[1] == 0) {
+        // one plane of such a grid (a 5-point stencil: classes -nx, -1, 0, 1, nx): registered alone
+        const int nx = sd.off[1], ny = (int)(n / sd.off[1]);
+        std::atomic<bool> cross{false};
+        if (pamg::pnc_tiled(nx, ny)) {
+            par_for(n, [&](int64_t a0, int64_t b0) {
+                for (int64_t i = a0; i < b0 && !cross; ++i) {
+                    const int x = (int)(i % nx), y = (int)(i / nx);
+                    const uint32_t m = mask[i];
+                    if (((m & 2u) && x == 0) || ((m & 8u) && x == nx - 1) || ((m & 1u) && y == 0) ||
+                        ((m & 16u) && y == ny - 1))
+                        cross = true;
+                }
+            });
+            if (!cross) register_grid(A->ctx, n, nx, ny, 1);
         }
     }
     A->sym = sd;

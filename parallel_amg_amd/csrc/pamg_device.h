@@ -174,7 +174,8 @@ struct Options {
     int ell_xwin_max = 7168;   // window capacity in doubles (<= kEllWinCap, the kernel's: 56 KB of its 60 KB of LDS)
     int pnc_compact = 1;       // 1: 16-bit combination ids instead of 64-bit records where <= kPncCombMax fit
     int pnc = 1;               // != 0: neighbour-coded prolongations over a grid registered on the context (PncSet);
-                               //    read per launch: 1 the tiled march where the plane cuts into tiles, 2 the line blocks
+                               //    read per launch, where the plane cuts into tiles: 1 the tiled march with the coarse
+                               //    values in LDS, 3 the one with the anchors in LDS; 2 (and other planes) the line blocks
     int sym_vd = 1;            // 1: row-class dictionary for the symmetric layout where the rows take <= kSymVdMax
                                //    distinct (mask, diagonal, upper values) tuples (SymDia::vd_n)
 };
@@ -317,9 +318,11 @@ constexpr int kPncSkip = kPncPatMax - 1;  // pattern id of a row outside the set
 // value indices (7 bits per entry from bit 0), npat = the combinations, d_rec = null.
 constexpr int kPncCombMax = 1024;
 constexpr int kPncCombSkip = 0xffff;
-// The tiled march (k_rows_pnct; Options::pnc == 1): a workgroup's 256 rows are a kPncTx x kPncTy
-// tile of a plane, where the plane cuts into whole tiles; else, and under Options::pnc == 2, 256
-// consecutive points of a line (k_rows_pnc). The PncSet arrays and the grid are the same for both.
+// The tiled march (Options::pnc == 1: k_rows_pncv, the tile's coarse values in LDS; == 3:
+// k_rows_pnct, its anchors in LDS): a workgroup's 256 rows are a kPncTx x kPncTy tile of a plane,
+// where the plane cuts into whole tiles; else, and under Options::pnc == 2, 256 consecutive points
+// of a line (k_rows_pnc). The PncSet arrays and the grid are the same for all three. A 7-point
+// grid registers on the context where its planes cut into these tiles (matrix.hip).
 constexpr int kPncTx = 64, kPncTy = 4;
 constexpr bool pnc_tiled(int nx, int ny) { return nx % kPncTx == 0 && ny % kPncTy == 0; }
 struct PncSet {

@@ -2507,7 +2507,7 @@ const OptionRow kOptionTable[] = {
     {"tb_xfast", &O::tb_xfast, 0, 1, false},
     {"ell", &O::ell, 0, 1, false},
     {"ell_restrict", &O::ell_restrict, 0, 1, false},
-    {"pnc", &O::pnc, 0, 2, false},
+    {"pnc", &O::pnc, 0, 3, false},
     {"rpat", &O::rpat, 0, 1, false},
     {"pnc_compact", &O::pnc_compact, 0, 1, false},
     {"ell_pair", &O::ell_pair, 0, 1, false},

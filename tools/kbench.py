@@ -63,7 +63,7 @@ def main():
     ap.add_argument("--ops", default="0,2")
     ap.add_argument("--mats", default=None, help="comma list of level matrices to run (e.g. R0,A1); default all")
     ap.add_argument("--ab", default=None,
-                    help="launch-time option to A/B on the same upload: KEY (values 0,1,0,1) or KEY=a,b "
+                    help="launch-time option to A/B on the same upload: KEY (values 0,1,0,1) or KEY=a,b[,c] "
                          "(a,b,a,b; e.g. symd_chunks=1,2)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="extra pamg_set_option before the uploads (e.g. band_pct=50)")
@@ -74,8 +74,7 @@ def main():
     ab_vals = (0, 1, 0, 1)
     if args.ab and "=" in args.ab:
         args.ab, vs = args.ab.split("=")
-        a_, b_ = (int(v) for v in vs.split(","))
-        ab_vals = (a_, b_, a_, b_)
+        ab_vals = tuple(int(v) for v in vs.split(",")) * 2  # (three values: a,b,c,a,b,c)
     for kv in args.set:
         k, v = kv.split("=")
         set_opts(**{k: int(v)})
