@@ -213,6 +213,24 @@ int pamg_mat_upload_blocked(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, c
 int pamg_mat_upload_block_rows(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, const int64_t* rowptr,
                                const void* col, int col_is_64, const double* val, int index_base,
                                const pamg_plan* col_plan, int bs, pamg_mat** out);
+/* Operator values stored in binary32 (SPEC §S15; optional). The caller passes fp64 values; the upload rounds
+ * each to binary32 (nearest even; subnormals and signed zeros kept, non-finite values as they are) and the
+ * operator is A~, a~_ij = (double)RN32(a_ij), in every respect: every call on the matrix has the bits of the
+ * same call on an fp64 upload of the array a~, whichever layout it takes. bs = 1: pamg_mat_upload of the
+ * rounded values; bs > 1, rect = 0: the checks and behaviour of pamg_mat_upload_blocked; rect = 1: those of
+ * pamg_mat_upload_block_rows (PAMG_BSR_ROW_LANES included). In the block-row layout, either form, the values
+ * are stored as 4-byte floats (4 + 4 / bs^2 bytes per nonzero a lane per node, 4 + 4 / bs a lane per row;
+ * pamg_mat_layout out[9] bit 16) and widened exactly in the kernel before the fp64 product; a matrix that
+ * declines that layout, or bs = 1, stores the rounded values as fp64 in the layouts it gets today. PAMG_E_ARG
+ * for a finite value that rounds to an infinity (|a| >= 2^128 - 2^103): the message names the first such
+ * entry's row and column, nothing is allocated and the context stays usable. */
+int pamg_mat_upload_f32(pamg_ctx* ctx, int64_t nrows, int64_t ncols_local, const int64_t* rowptr,
+                        const void* col, int col_is_64, const double* val, int index_base,
+                        const pamg_plan* col_plan, int bs, int rect, pamg_mat** out);
+/* 32 for a matrix uploaded through pamg_mat_upload_f32 (whatever its storage), 64 otherwise: the mark tells
+ * which entry point made the matrix, so values a caller rounded itself and passed to another upload
+ * (pamg_mat_upload_perm has no binary32 variant) read 64. */
+int pamg_mat_value_bits(const pamg_mat* A, int* bits);
 int pamg_mat_destroy(pamg_mat* A);
 int pamg_mat_info(const pamg_mat* A, int64_t* nrows, int64_t* ncols_local, int64_t* nnz);
 /* Bytes of matrix data one row operation streams in the layout chosen at upload: 8 B values +
@@ -252,7 +270,8 @@ int pamg_mat_stream_bytes(const pamg_mat* A, int64_t* bytes);
  * bit 15: the set runs in the block-row layout (bsr; pamg_mat_upload_blocked, pamg_mat_upload_block_rows:
  * then out[3] = the block size, out[4] = the padded block slots, out[8] = the kernel's grid, and out[6] = 1
  * where a restriction-shaped operator took the row-per-lane form — a lane per scalar row, the slots per
- * row with bs values each). */
+ * row with bs values each); bit 16: with bit 15 only, the set stores 4-byte values (pamg_mat_upload_f32,
+ * SPEC §S15; pamg_mat_stream_bytes counts 4 B per value there). */
 int pamg_mat_layout(const pamg_mat* A, int set, int out[10]);
 /* The windowed sliced-ELL layout of a matrix (ell_xwin; with pamg_mat_layout bits 9 and 13): out[0]
  * 1 where the matrix runs in it (else all 0), out[1] the groups whose x window is staged in LDS,
@@ -392,6 +411,14 @@ int pamg_hier_set_smoother(pamg_hier* H, int kind, const double* lmax, double ra
  * order: pamg_vcycle's res_hist norms and pamg_pcg's dot products — hence its iterates — match
  * the unpermuted run to rounding only, not bit for bit. perm = NULL (or n = 0) removes it. */
 int pamg_hier_set_perm(pamg_hier* H, int64_t n, const int64_t* perm);
+/* The outer operator of the hierarchy's PCG solves (SPEC §S15): pamg_pcg, pamg_pcg_resident and pamg_pcg_multi
+ * form b - A x and A p with A instead of the hierarchy's level-0 operator, and the V-cycle stays the
+ * hierarchy's — the exact fp64 operator around a hierarchy of operators rounded to binary32. A = NULL
+ * restores level 0's own. The hierarchy does not own A: it must outlive the solves. PAMG_E_ARG unless A has
+ * level 0's shape and its column plan (the same handle, or none on both); PAMG_E_STATE on a hierarchy with a
+ * level-0 permutation (pamg_hier_set_perm, which in turn refuses a hierarchy with an outer operator). Drops the
+ * graphs of pamg_pcg_resident. pamg_vcycle and its res_hist are untouched: they iterate on level 0's own. */
+int pamg_hier_set_outer(pamg_hier* H, const pamg_mat* A);
 /* enabled: graph replay currently on; captured: a graph exists; failed: a capture failed. */
 int pamg_hier_graph_state(const pamg_hier* H, int* enabled, int* captured, int* failed);
 /* x <- V(x) ncycles times (SPEC §S6); res_hist (ncycles, may be NULL) gets ||b - A x||. */

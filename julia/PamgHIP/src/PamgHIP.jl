@@ -26,7 +26,7 @@ export Context, ExchangePlan, DeviceVector, DeviceMatrix, HostCSR, VCycle, Excha
        download_own, download_ghosts, exchange_begin, residual!, jacobi!, jacobi_residual!, chebyshev!, chebyshev_coeffs, vcycle!, pcg!, set_sweeps!, set_smoother!,
        fill_xstar!, estimate_lmax, set_omega!, block_diag, set_block_diag!, block_size, block_jacobi!, block_chebyshev!,
        estimate_lmax_block, DeviceMultiVector, column, spmm!, mvec_size,
-       set_perm!, setup_hierarchy, gen_grid, gen_xstar, read_mtx, rcm_order, locality_order, unique_id,
+       set_perm!, set_outer!, value_bits, setup_hierarchy, gen_grid, gen_xstar, read_mtx, rcm_order, locality_order, unique_id,
        comm_init!, runtime_versions, hip, World, world_spmv!, world_exchange!, world_dot, world_vcycle!,
        world_pcg!, world_abort!, world_reset!, world_broken, set_tag!
 
@@ -354,7 +354,7 @@ mutable struct DeviceMatrix
 end
 """
     DeviceMatrix(ctx, rowptr, col, val, ncols_local; plan = nothing, index_base = 1,
-                 row_perm = nothing, col_perm = nothing, block_size = 1, block_rows = 1)
+                 row_perm = nothing, col_perm = nothing, block_size = 1, block_rows = 1, value_bits = 64)
 
 One part's own rows in CSR with LOCAL column ids (own columns first, then the plan's ghost
 slots), each row in ascending global column order (SPEC §S1). Int64 or Int32 columns, 1- or
@@ -366,13 +366,19 @@ that many unknowns per node takes the block-row layout where every node's rows s
 blocks and no row has a ghost column (`layout(A).bsr`; same bits), else the layouts of a plain upload.
 `block_rows` > 1 (pamg_mat_upload_block_rows): the same for an operator that may be rectangular, between
 two node-major spaces of that block size — the P and R of a nodal hierarchy (SPEC §S14); no diagonal is asked.
+`value_bits = 32` (pamg_mat_upload_f32, SPEC §S15; not with a permutation): the values are rounded to Float32 and
+the operator is the rounded one in every respect; in the block-row layout they are stored as 4-byte floats
+(`layout(A).bsr_f32`), elsewhere as Float64. A value that overflows Float32 is an argument error.
 """
 function DeviceMatrix(ctx::Context, rowptr::AbstractVector{<:Integer}, col::AbstractVector{<:Integer},
                       val::AbstractVector{<:Real}, ncols_local::Integer;
                       plan::Union{Nothing,ExchangePlan} = nothing, index_base::Integer = 1,
                       row_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing,
                       col_perm::Union{Nothing,AbstractVector{<:Integer}} = nothing,
-                      block_size::Integer = 1, block_rows::Integer = 1)
+                      block_size::Integer = 1, block_rows::Integer = 1, value_bits::Integer = 64)
+    value_bits in (32, 64) || throw(ArgumentError("DeviceMatrix: value_bits is 32 or 64"))
+    value_bits == 32 && (row_perm !== nothing || col_perm !== nothing) &&
+        throw(ArgumentError("DeviceMatrix: value_bits = 32 cannot be combined with row_perm / col_perm"))
     (block_size != 1 || block_rows != 1) && (row_perm !== nothing || col_perm !== nothing) &&
         throw(ArgumentError("DeviceMatrix: block_size > 1 cannot be combined with row_perm / col_perm"))
     block_size != 1 && block_rows != 1 &&
@@ -382,7 +388,13 @@ function DeviceMatrix(ctx::Context, rowptr::AbstractVector{<:Integer}, col::Abst
     is64 = eltype(c) == Int64 ? Cint(1) : Cint(0)
     v = Vector{Float64}(val)
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    if block_size != 1
+    if value_bits == 32
+        check(ccall((:pamg_mat_upload_f32, libpamg), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Cvoid}, Cint, Cint,
+                     Ptr{Ptr{Cvoid}}),
+                    ctx.h, length(rp) - 1, ncols_local, rp, c, is64, v, index_base,
+                    plan === nothing ? C_NULL : plan.h, max(block_size, block_rows), block_rows != 1 ? 1 : 0, h))
+    elseif block_size != 1
         check(ccall((:pamg_mat_upload_blocked, libpamg), Cint,
                     (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Ptr{Cvoid}, Cint,
                      Ptr{Ptr{Cvoid}}),
@@ -437,7 +449,13 @@ function layout(A::DeviceMatrix, set::Integer = 0)
     check(ccall((:pamg_mat_layout, libpamg), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}), A.h, set, out))
     (c24 = out[1] != 0, vd = out[2] != 0, rl8 = out[3] != 0, cd = Int(out[4]), cd_offsets = Int(out[5]),
      tm = out[6] != 0, tm_rs = Int(out[7]), tile_nnz = Int(out[8]), tiles = Int(out[9]), anchored = (out[10] & 1) != 0, per_tile = (out[10] & 2) != 0,
-     x_stage = (out[10] & 4) != 0, bsr = (out[10] & 32768) != 0)
+     x_stage = (out[10] & 4) != 0, bsr = (out[10] & 32768) != 0, bsr_f32 = (out[10] & 65536) != 0)
+end
+"32 for a matrix uploaded with `value_bits = 32` (SPEC §S15), else 64."
+function value_bits(A::DeviceMatrix)
+    b = Ref{Cint}(0)
+    check(ccall((:pamg_mat_value_bits, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cint}), A.h, b))
+    Int(b[])
 end
 "The windowed sliced-ELL layout of a matrix (`ell_xwin`): whether it runs in it, its windowed and gathering groups, the largest window."
 function ell_window(A::DeviceMatrix)
@@ -759,6 +777,18 @@ function set_perm!(M::VCycle, perm::Union{Nothing,AbstractVector{<:Integer}})
     p = perm === nothing ? Int64[] : Int64.(perm) .- 1
     check(ccall((:pamg_hier_set_perm, libpamg), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}), M.h, length(p),
                 isempty(p) ? Ptr{Int64}(C_NULL) : p))
+    M
+end
+const OUTER = WeakKeyDict{VCycle,DeviceMatrix}()  # kept alive: the hierarchy references it
+"""
+    set_outer!(M, A)
+
+The operator `pcg!` forms b - A x and A p with (SPEC §S15: the exact operator around a hierarchy of operators
+rounded to Float32); `nothing` restores level 0's own. `A` has level 0's shape and column plan.
+"""
+function set_outer!(M::VCycle, A::Union{Nothing,DeviceMatrix})
+    check(ccall((:pamg_hier_set_outer, libpamg), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), M.h, A === nothing ? C_NULL : A.h))
+    A === nothing ? delete!(OUTER, M) : (OUTER[M] = A)
     M
 end
 function graph_state(M::VCycle)

@@ -81,6 +81,8 @@ SIGNATURES = {
     "pamg_mat_upload_perm": [vp, i64, i64, vp, vp, i32, vp, i32, vp, vp, vp, pvp],
     "pamg_mat_upload_blocked": [vp, i64, i64, vp, vp, i32, vp, i32, vp, i32, pvp],
     "pamg_mat_upload_block_rows": [vp, i64, i64, vp, vp, i32, vp, i32, vp, i32, pvp],
+    "pamg_mat_upload_f32": [vp, i64, i64, vp, vp, i32, vp, i32, vp, i32, i32, pvp],
+    "pamg_mat_value_bits": [vp, C.POINTER(C.c_int)],
     "pamg_mat_destroy": [vp],
     "pamg_mat_info": [vp, pi64, pi64, pi64],
     "pamg_mat_stream_bytes": [vp, pi64],
@@ -107,6 +109,7 @@ SIGNATURES = {
     "pamg_hier_set_sweeps": [vp, i32, i32],
     "pamg_hier_set_smoother": [vp, i32, vp, dbl],
     "pamg_hier_set_perm": [vp, i64, vp],
+    "pamg_hier_set_outer": [vp, vp],
     "pamg_hier_graph_state": [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "pamg_vcycle": [vp, vp, vp, vp, i32, vp],
     "pamg_vcycle_async": [vp, vp, vp, vp, i32],
@@ -266,7 +269,8 @@ def layout_of(M, part_set: int = 0) -> dict:
             "ell_pair": bool(out[9] & 8192), "pnc_tiled": bool(out[9] & 16384),
             "bsr": bool(out[9] & 32768),
             # with bsr: the row-per-lane form (a lane per scalar row: restriction-shaped block-row operators)
-            "bsr_row_lanes": bool(out[9] & 32768) and out[6] == 1}  # (ell_xwin*: pamg_mat_ell_window)
+            "bsr_row_lanes": bool(out[9] & 32768) and out[6] == 1,
+            "bsr_f32": bool(out[9] & 65536)}  # 4-byte values (SPEC §S15)  (ell_xwin*: pamg_mat_ell_window)
 
 
 def last_error() -> str:

@@ -9,6 +9,9 @@
 // are epilogue<OP>'s and the fused block sweeps k_rows_bsr's, per column, with the diagonal entries and
 // the lane's d_binv block loaded once. No LDS, no barrier.
 // A unit of its own: kernels.hip's code object stays as it is ("Several right-hand sides").
+// Values stored in binary32 (SPEC §S15; BsrSet::d_val32): the kernels' VT = float instantiations load the same
+// slots as 4-byte values — 4 + 4 / bs^2 bytes per nonzero — and widen each exactly, (double)v, before the fp64
+// product, so the sums are those of an fp64 upload of the rounded values.
 
 #include "multi_cols.h"
 #include "pamg_device.h"
@@ -28,9 +31,10 @@ struct McOut {
     double* p[NV];
 };
 
-template <int BS, int OP, int FUSE, int NV>
+// VT: the stored value type (SPEC §S15: float values are widened exactly before the fp64 product)
+template <int BS, int OP, int FUSE, int NV, typename VT = double>
 __global__ __launch_bounds__(kBlock) void k_rows_bsr_mc(int nb, int ns, const int64_t* __restrict__ soff,
-                                                        const int* __restrict__ bcol, const double* __restrict__ val,
+                                                        const int* __restrict__ bcol, const VT* __restrict__ val,
                                                         const double* __restrict__ diag,
                                                         const double* __restrict__ binv, int x16, McIn<NV> x,
                                                         McIn<NV> b, McOut<NV> y, double omega, double c1,
@@ -47,13 +51,13 @@ __global__ __launch_bounds__(kBlock) void k_rows_bsr_mc(int nb, int ns, const in
         for (int d = 0; d < BS; ++d) s[c][d] = 0.0;
     }
     const int* cp = bcol + k0 * kEllW + lane;
-    const double* vp = val + k0 * (BS * BS) * kEllW + lane;
+    const VT* vp = val + k0 * (BS * BS) * kEllW + lane;
     for (int64_t k = k0; k < k1; ++k, cp += kEllW, vp += BS * BS * kEllW) {
         const int col = *cp;
         if (col < 0) continue;
         double v[BS * BS];
 #pragma unroll
-        for (int j = 0; j < BS * BS; ++j) v[j] = vp[j * kEllW];
+        for (int j = 0; j < BS * BS; ++j) v[j] = (double)vp[j * kEllW];
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             double xe[BS];
@@ -131,14 +135,22 @@ void launch_chunk(const pamg_mat& A, const double* const* x, const double* const
         ya.p[c] = y[c];
         if ((reinterpret_cast<uintptr_t>(x[c]) & 15) != 0) x16 = 0;
     }
-    auto go = [&](auto kern) {
-        kern<<<B.grid, kBlock, 0, s>>>((int)B.nb, (int)B.nslices, B.d_soff, B.d_bcol, B.d_val, A.d_diag, A.d_binv, x16,
+    auto go = [&](auto kern, auto* val) {
+        kern<<<B.grid, kBlock, 0, s>>>((int)B.nb, (int)B.nslices, B.d_soff, B.d_bcol, val, A.d_diag, A.d_binv, x16,
                                        xa, ba, ya, omega, c1, oa);
     };
+    if (B.d_val32) {
+        switch (B.bs) {
+            case 2: go(k_rows_bsr_mc<2, OP, FUSE, NV, float>, B.d_val32); break;
+            case 3: go(k_rows_bsr_mc<3, OP, FUSE, NV, float>, B.d_val32); break;
+            default: go(k_rows_bsr_mc<4, OP, FUSE, NV, float>, B.d_val32); break;
+        }
+        return;
+    }
     switch (B.bs) {
-        case 2: go(k_rows_bsr_mc<2, OP, FUSE, NV>); break;
-        case 3: go(k_rows_bsr_mc<3, OP, FUSE, NV>); break;
-        default: go(k_rows_bsr_mc<4, OP, FUSE, NV>); break;
+        case 2: go(k_rows_bsr_mc<2, OP, FUSE, NV>, B.d_val); break;
+        case 3: go(k_rows_bsr_mc<3, OP, FUSE, NV>, B.d_val); break;
+        default: go(k_rows_bsr_mc<4, OP, FUSE, NV>, B.d_val); break;
     }
 }
 
@@ -168,6 +180,26 @@ void launch_chunk_op(const pamg_mat& A, int op, int fuse, const double* const* x
 // loaded before its first product (a padded slot holds column -1 and zeros: its loads are in bounds, its
 // products are skipped), so four dependent x loads are in flight per lane instead of one. No LDS, no barrier.
 // OP_SPMV, OP_RESID and OP_PROLONG only: the form is built for operators that are not square.
+// (binary32 values, SPEC §S15: BS adjacent floats, one 8- or 16-byte load for BS 2 or 4, widened exactly)
+template <int BS>
+__device__ __forceinline__ void bsr_r_load_v(const float* __restrict__ p, double (&v)[BS]) {
+    if constexpr (BS == 2) {
+        const float2 t = *reinterpret_cast<const float2*>(p);
+        v[0] = (double)t.x;
+        v[1] = (double)t.y;
+    } else if constexpr (BS == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = (double)t.x;
+        v[1] = (double)t.y;
+        v[2] = (double)t.z;
+        v[3] = (double)t.w;
+    } else {
+        v[0] = (double)p[0];
+        v[1] = (double)p[1];
+        v[2] = (double)p[2];
+    }
+}
+
 template <int BS>
 __device__ __forceinline__ void bsr_r_load_v(const double* __restrict__ p, double (&v)[BS]) {
     if constexpr (BS == 3) {
@@ -184,9 +216,9 @@ __device__ __forceinline__ void bsr_r_load_v(const double* __restrict__ p, doubl
     }
 }
 
-template <int BS, int OP, int NV>
+template <int BS, int OP, int NV, typename VT = double>
 __global__ __launch_bounds__(kBlock) void k_rows_bsr_r(int nrows, int ns, const int64_t* __restrict__ soff,
-                                                       const int* __restrict__ bcol, const double* __restrict__ val,
+                                                       const int* __restrict__ bcol, const VT* __restrict__ val,
                                                        int x16, McIn<NV> x, McIn<NV> b, McOut<NV> y) {
     constexpr int U = 4;
     const int lane = threadIdx.x & (kEllW - 1);
@@ -198,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_bsr_r(int nrows, int ns, const 
 #pragma unroll
     for (int c = 0; c < NV; ++c) s[c] = 0.0;
     const int* cp = bcol + k0 * kEllW + lane;
-    const double* vp = val + (k0 * kEllW + lane) * BS;
+    const VT* vp = val + (k0 * kEllW + lane) * BS;
     auto slot = [&](int col, const double (&v)[BS]) {
         if (col < 0) return;
 #pragma unroll
@@ -246,13 +278,21 @@ void launch_rows_chunk(const pamg_mat& A, const double* const* x, const double* 
         ya.p[c] = y[c];
         if ((reinterpret_cast<uintptr_t>(x[c]) & 15) != 0) x16 = 0;
     }
-    auto go = [&](auto kern) {
-        kern<<<B.grid, kBlock, 0, s>>>((int)A.nrows, (int)B.nslices, B.d_soff, B.d_bcol, B.d_val, x16, xa, ba, ya);
+    auto go = [&](auto kern, auto* val) {
+        kern<<<B.grid, kBlock, 0, s>>>((int)A.nrows, (int)B.nslices, B.d_soff, B.d_bcol, val, x16, xa, ba, ya);
     };
+    if (B.d_val32) {
+        switch (B.bs) {
+            case 2: go(k_rows_bsr_r<2, OP, NV, float>, B.d_val32); break;
+            case 3: go(k_rows_bsr_r<3, OP, NV, float>, B.d_val32); break;
+            default: go(k_rows_bsr_r<4, OP, NV, float>, B.d_val32); break;
+        }
+        return;
+    }
     switch (B.bs) {
-        case 2: go(k_rows_bsr_r<2, OP, NV>); break;
-        case 3: go(k_rows_bsr_r<3, OP, NV>); break;
-        default: go(k_rows_bsr_r<4, OP, NV>); break;
+        case 2: go(k_rows_bsr_r<2, OP, NV>, B.d_val); break;
+        case 3: go(k_rows_bsr_r<3, OP, NV>, B.d_val); break;
+        default: go(k_rows_bsr_r<4, OP, NV>, B.d_val); break;
     }
 }
 

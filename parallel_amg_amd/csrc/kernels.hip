@@ -3395,9 +3395,10 @@ __global__ void k_pcg_dir(int64_t n, const PcgScalars* S, const double* __restri
 // Chebyshev step; OP_RESID) apply D_m^-1 from the lane's BS^2 entries of d_binv in registers — k_block_update's
 // roundings in its order, with no second pass and no LDS. No barrier: a wave past the last slice leaves.
 // (bsr_load_x, a block's BS entries of x: row_epilogue.h, shared with bsr_multi.hip)
-template <int BS, int OP, int FUSE>
+// VT: the stored value type (SPEC §S15) — float values are widened exactly, (double)v, before the fp64 product.
+template <int BS, int OP, int FUSE, typename VT = double>
 __global__ __launch_bounds__(kBlock) void k_rows_bsr(int nb, int ns, const int64_t* __restrict__ soff,
-                                                     const int* __restrict__ bcol, const double* __restrict__ val,
+                                                     const int* __restrict__ bcol, const VT* __restrict__ val,
                                                      const double* __restrict__ diag,
                                                      const double* __restrict__ binv, int x16,
                                                      const double* __restrict__ x, const double* __restrict__ b,
@@ -3412,14 +3413,14 @@ __global__ __launch_bounds__(kBlock) void k_rows_bsr(int nb, int ns, const int64
 #pragma unroll
     for (int d = 0; d < BS; ++d) s[d] = 0.0;
     const int* cp = bcol + k0 * kEllW + lane;
-    const double* vp = val + k0 * (BS * BS) * kEllW + lane;
+    const VT* vp = val + k0 * (BS * BS) * kEllW + lane;
     for (int64_t k = k0; k < k1; ++k, cp += kEllW, vp += BS * BS * kEllW) {
         const int c = *cp;
         if (c < 0) continue;
         double xe[BS], v[BS * BS];
         bsr_load_x<BS>(x, c, x16 != 0, xe);
 #pragma unroll
-        for (int j = 0; j < BS * BS; ++j) v[j] = vp[j * kEllW];
+        for (int j = 0; j < BS * BS; ++j) v[j] = (double)vp[j * kEllW];
 #pragma unroll
         for (int d = 0; d < BS; ++d) {
 #pragma unroll
@@ -3472,14 +3473,22 @@ void launch_bsr(const pamg_mat& A, const double* x, const double* b, double* y, 
     const BsrSet& B = A.bsr;
     if (B.nb <= 0) return;
     const int x16 = (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? 1 : 0;
-    auto go = [&](auto kern) {
-        kern<<<B.grid, kBlock, 0, s>>>((int)B.nb, (int)B.nslices, B.d_soff, B.d_bcol, B.d_val, A.d_diag, A.d_binv, x16,
+    auto go = [&](auto kern, auto* val) {
+        kern<<<B.grid, kBlock, 0, s>>>((int)B.nb, (int)B.nslices, B.d_soff, B.d_bcol, val, A.d_diag, A.d_binv, x16,
                                        x, b, y, omega, ch.c1, ch.xold);
     };
+    if (B.d_val32) {  // binary32 values (SPEC §S15)
+        switch (B.bs) {
+            case 2: go(k_rows_bsr<2, OP, FUSE, float>, B.d_val32); break;
+            case 3: go(k_rows_bsr<3, OP, FUSE, float>, B.d_val32); break;
+            default: go(k_rows_bsr<4, OP, FUSE, float>, B.d_val32); break;
+        }
+        return;
+    }
     switch (B.bs) {
-        case 2: go(k_rows_bsr<2, OP, FUSE>); break;
-        case 3: go(k_rows_bsr<3, OP, FUSE>); break;
-        default: go(k_rows_bsr<4, OP, FUSE>); break;
+        case 2: go(k_rows_bsr<2, OP, FUSE>, B.d_val); break;
+        case 3: go(k_rows_bsr<3, OP, FUSE>, B.d_val); break;
+        default: go(k_rows_bsr<4, OP, FUSE>, B.d_val); break;
     }
 }
 }  // namespace

@@ -1903,8 +1903,24 @@ void pnc_free(pamg::PncSet& P) {
 // whole, and the kernel's walk "blocks in order, e = 0 .. bs - 1 inside" the row's stored order (SPEC §S3).
 // Otherwise nothing is built.
 // row_lanes: the row-per-lane form (BsrSet::row_lanes, TileSet::bsr_r) instead of one lane per node.
-int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs);
-int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs, bool row_lanes = false) {
+// f32 (SPEC §S15): val holds values exact in binary32, and the slots are stored as float in d_val32.
+int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs, bool f32);
+// the slot values on the device: as they are, or narrowed (exactly) to binary32
+int bsr_put_values(pamg_ctx* ctx, pamg::BsrSet& B, const std::vector<double>& bval, int64_t min_count, bool f32) {
+    const int64_t n = std::max<int64_t>((int64_t)bval.size(), min_count);
+    if (!f32) {
+        CHECK(dalloc(&B.d_val, n));
+        return h2d(ctx, B.d_val, bval.data(), sizeof(double) * bval.size());
+    }
+    std::vector<float> v32(bval.size());
+    par_for((int64_t)bval.size(), [&](int64_t a, int64_t b) {
+        for (int64_t i = a; i < b; ++i) v32[i] = (float)bval[i];
+    });
+    CHECK(dalloc(&B.d_val32, n));
+    return h2d(ctx, B.d_val32, v32.data(), sizeof(float) * v32.size());
+}
+int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs, bool row_lanes = false,
+              bool f32 = false) {
     using pamg::kEllW;
     pamg_ctx* ctx = A->ctx;
     const int64_t nb = A->nrows / bs, ns = (nb + kEllW - 1) / kEllW;
@@ -1924,7 +1940,7 @@ int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
         }
     });
     if (!ok) return PAMG_OK;
-    if (row_lanes) return build_bsr_rows(A, rp, ci, val, bs);
+    if (row_lanes) return build_bsr_rows(A, rp, ci, val, bs, f32);
     pamg::BsrSet& B = A->bsr;
     std::vector<int64_t> soff(ns + 1, 0);
     for (int64_t s = 0; s < ns; ++s) {
@@ -1950,10 +1966,9 @@ int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
     });
     CHECK(dalloc(&B.d_soff, ns + 1));
     CHECK(dalloc(&B.d_bcol, std::max<int64_t>(slots, 1)));
-    CHECK(dalloc(&B.d_val, std::max<int64_t>(slots * b2, 1)));
     CHECK(h2d(ctx, B.d_soff, soff.data(), sizeof(int64_t) * (ns + 1)));
     CHECK(h2d(ctx, B.d_bcol, bcol.data(), sizeof(int) * bcol.size()));
-    CHECK(h2d(ctx, B.d_val, bval.data(), sizeof(double) * bval.size()));
+    CHECK(bsr_put_values(ctx, B, bval, 1, f32));
     B.bs = bs;
     B.nb = nb;
     B.nslices = ns;
@@ -1965,7 +1980,7 @@ int build_bsr(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val
 
 // The row-per-lane form of a matrix build_bsr has checked: a sliced ELL over scalar rows, a block column and
 // the row's bs entries of the block per slot (pamg_device.h, BsrSet).
-int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs) {
+int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double* val, int bs, bool f32) {
     using pamg::kEllW;
     pamg_ctx* ctx = A->ctx;
     const int64_t n = A->nrows, ns = (n + kEllW - 1) / kEllW;
@@ -1992,10 +2007,9 @@ int build_bsr_rows(pamg_mat* A, const PtrVec& rp, const IdxVec& ci, const double
     });
     CHECK(dalloc(&B.d_soff, ns + 1));
     CHECK(dalloc(&B.d_bcol, std::max<int64_t>(slots, 1)));
-    CHECK(dalloc(&B.d_val, std::max<int64_t>(slots * bs, 2)));
     CHECK(h2d(ctx, B.d_soff, soff.data(), sizeof(int64_t) * (ns + 1)));
     CHECK(h2d(ctx, B.d_bcol, bcol.data(), sizeof(int) * bcol.size()));
-    CHECK(h2d(ctx, B.d_val, bval.data(), sizeof(double) * bval.size()));
+    CHECK(bsr_put_values(ctx, B, bval, 4, f32));
     B.bs = bs;
     B.nb = n / bs;
     B.nslices = ns;
@@ -2024,7 +2038,7 @@ int bsr_try(Upload& u) {
     if (u.bs > 1 && shape && u.bnd.empty() && A->nrows > 0 && A->nrows % u.bs == 0) {
         // (few, long block rows: a lane per scalar row where that form is wanted)
         const bool row_lanes = u.rect && A->nrows < u.n_own_cols && bsr_row_lanes();
-        CHECK(build_bsr(A, u.rp, u.ci, u.val, u.bs, row_lanes));
+        CHECK(build_bsr(A, u.rp, u.ci, u.val, u.bs, row_lanes, A->value_bits == 32));
         if (pamg::bsr_any(*A)) u.inner.clear();  // the rows run in k_rows_bsr / k_rows_bsr_r, not in tiles
         u.tr.mark("bsr");
     }
@@ -2035,7 +2049,8 @@ int bsr_try(Upload& u) {
 int64_t bsr_bytes(const pamg_mat* A) {
     if (!pamg::bsr_any(*A)) return 0;
     const int64_t per_slot = A->bsr.row_lanes ? A->bsr.bs : (int64_t)A->bsr.bs * A->bsr.bs;
-    return A->bsr.slots * (4 + 8 * per_slot) + 8 * (A->bsr.nslices + 1);
+    const int64_t vbytes = A->bsr.d_val32 ? 4 : 8;  // (SPEC §S15: binary32 slots)
+    return A->bsr.slots * (4 + vbytes * per_slot) + 8 * (A->bsr.nslices + 1);
 }
 
 void bsr_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
@@ -2045,12 +2060,14 @@ void bsr_report(const pamg_mat* A, const pamg::TileSet& t, int out[10]) {
     out[6] = t.bsr_r ? 1 : 0;  // the row-per-lane form: the slots are per scalar row (bs values each)
     out[8] = A->bsr.grid;
     out[9] |= 32768;
+    if (A->bsr.d_val32) out[9] |= 65536;  // the set stores 4-byte values (SPEC §S15)
 }
 
 void bsr_free(pamg::BsrSet& B) {
     dfree(B.d_soff);
     dfree(B.d_bcol);
     dfree(B.d_val);
+    dfree(B.d_val32);
     B = pamg::BsrSet{};
 }
 
@@ -2877,7 +2894,8 @@ void tiles_free(pamg::TileSet& ts) {
 // checked; rect: the latter): the block-row family is tried first for those two alone; where it declines the
 // matrix goes on exactly as bs = 1 does
 int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr, const void* col, int col_is_64,
-               const double* val, int index_base, const pamg_plan* plan, int bs, pamg_mat** out, bool rect = false) {
+               const double* val, int index_base, const pamg_plan* plan, int bs, pamg_mat** out, bool rect = false,
+               int value_bits = 64) {
     if (!ctx || !out || nrows < 0 || ncols < 0 || !rowptr || (index_base != 0 && index_base != 1))
         return fail(PAMG_E_ARG, "mat_upload: bad args");
     const int64_t nnz = rowptr[nrows] - index_base;
@@ -2933,6 +2951,35 @@ int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowpt
         }
     }
     tr.mark("columns");
+    // SPEC §S15: the operator is A~, a~_ij = (double)RN32(a_ij) — rounded here, before any family sees a value,
+    // so every layout, diagonal and block is A~'s; the block-row layouts store the floats themselves. A finite
+    // value that rounds to an infinity is refused before anything is allocated.
+    std::vector<double> rounded;
+    if (value_bits == 32 && nnz > 0) {
+        rounded.resize(nnz);
+        std::atomic<int64_t> bad_at{INT64_MAX};
+        par_for(nnz, [&](int64_t a, int64_t b) {
+            for (int64_t k = a; k < b; ++k) {
+                const float f = (float)val[k];  // round to nearest even; subnormals and signed zeros kept
+                if (std::isinf(f) && std::isfinite(val[k])) {
+                    int64_t cur = bad_at.load();
+                    while (k < cur && !bad_at.compare_exchange_weak(cur, k)) {
+                    }
+                }
+                rounded[k] = (double)f;
+            }
+        });
+        if (bad_at.load() != INT64_MAX) {
+            const int64_t k = bad_at.load();
+            const int64_t row = std::upper_bound(rp.begin(), rp.end(), k) - rp.begin() - 1;
+            return fail(PAMG_E_ARG,
+                        "mat_upload_f32: the value %a of row %lld, column %lld (index base %d) rounds to an infinite "
+                        "binary32",
+                        val[k], (long long)(row + index_base), (long long)(ci[k] + index_base), index_base);
+        }
+        val = rounded.data();
+        tr.mark("round32");
+    }
     // released through pamg_mat_destroy on every error path (no device memory leaks)
     std::unique_ptr<pamg_mat, int (*)(pamg_mat*)> A(new pamg_mat, pamg_mat_destroy);
     A->ctx = ctx;
@@ -2941,6 +2988,7 @@ int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowpt
     A->ncols = ncols;
     A->nnz = nnz;
     A->plan = plan;
+    A->value_bits = value_bits;
     // classify rows: interior (own columns only) or boundary (>= 1 ghost column), and find
     // the diagonal (threads over row ranges)
     std::vector<int> inner, bnd;
@@ -3048,6 +3096,23 @@ int mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowpt
     return PAMG_OK;
 }
 
+// The argument checks of the block uploads (`who` names the entry point): bs in 1..4 and, with bs > 1, whole
+// blocks of rows, and a square operator (rect false) or whole blocks of own columns (rect true).
+int check_block_args(const char* who, const pamg_ctx* ctx, int64_t nrows, int64_t ncols, const pamg_plan* plan, int bs,
+                     bool rect) {
+    if (bs < 1 || bs > 4) return fail(PAMG_E_ARG, "%s: block size %d outside 1..4", who, bs);
+    if (bs > 1 && ctx && nrows >= 0 && ncols >= 0) {
+        const int64_t n_own_cols = plan ? plan->n_own : ncols;
+        if (!rect && nrows != n_own_cols)
+            return fail(PAMG_E_ARG, "%s: the operator must be square (%lld rows, %lld own columns)", who, (long long)nrows,
+                        (long long)n_own_cols);
+        if (nrows % bs != 0) return fail(PAMG_E_ARG, "%s: %lld rows are not whole blocks of %d", who, (long long)nrows, bs);
+        if (rect && n_own_cols % bs != 0)
+            return fail(PAMG_E_ARG, "%s: %lld own columns are not whole blocks of %d", who, (long long)n_own_cols, bs);
+    }
+    return PAMG_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ C-ABI: pamg_mat_*
@@ -3063,31 +3128,31 @@ int pamg_mat_upload(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* 
 int pamg_mat_upload_blocked(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr,
                             const void* col, int col_is_64, const double* val, int index_base,
                             const pamg_plan* plan, int bs, pamg_mat** out) {
-    if (bs < 1 || bs > 4) return fail(PAMG_E_ARG, "mat_upload_blocked: block size %d outside 1..4", bs);
-    if (bs > 1 && ctx && nrows >= 0 && ncols >= 0) {
-        const int64_t n_own_cols = plan ? plan->n_own : ncols;
-        if (nrows != n_own_cols)
-            return fail(PAMG_E_ARG, "mat_upload_blocked: the operator must be square (%lld rows, %lld own columns)",
-                        (long long)nrows, (long long)n_own_cols);
-        if (nrows % bs != 0)
-            return fail(PAMG_E_ARG, "mat_upload_blocked: %lld rows are not whole blocks of %d", (long long)nrows, bs);
-    }
+    CHECK(check_block_args("mat_upload_blocked", ctx, nrows, ncols, plan, bs, false));
     return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, bs, out);
 }
 
 int pamg_mat_upload_block_rows(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr,
                                const void* col, int col_is_64, const double* val, int index_base,
                                const pamg_plan* plan, int bs, pamg_mat** out) {
-    if (bs < 1 || bs > 4) return fail(PAMG_E_ARG, "mat_upload_block_rows: block size %d outside 1..4", bs);
-    if (bs > 1 && ctx && nrows >= 0 && ncols >= 0) {
-        const int64_t n_own_cols = plan ? plan->n_own : ncols;
-        if (nrows % bs != 0)
-            return fail(PAMG_E_ARG, "mat_upload_block_rows: %lld rows are not whole blocks of %d", (long long)nrows, bs);
-        if (n_own_cols % bs != 0)
-            return fail(PAMG_E_ARG, "mat_upload_block_rows: %lld own columns are not whole blocks of %d",
-                        (long long)n_own_cols, bs);
-    }
+    CHECK(check_block_args("mat_upload_block_rows", ctx, nrows, ncols, plan, bs, true));
     return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, bs, out, bs > 1);
+}
+
+// SPEC §S15: either block upload, or the plain one, of the values rounded to binary32 (mat_upload rounds them
+// after its own checks and marks the matrix).
+int pamg_mat_upload_f32(pamg_ctx* ctx, int64_t nrows, int64_t ncols, const int64_t* rowptr, const void* col,
+                        int col_is_64, const double* val, int index_base, const pamg_plan* plan, int bs, int rect,
+                        pamg_mat** out) {
+    if (rect != 0 && rect != 1) return fail(PAMG_E_ARG, "mat_upload_f32: rect is %d, not 0 or 1", rect);
+    CHECK(check_block_args("mat_upload_f32", ctx, nrows, ncols, plan, bs, rect != 0));
+    return mat_upload(ctx, nrows, ncols, rowptr, col, col_is_64, val, index_base, plan, bs, out, bs > 1 && rect, 32);
+}
+
+int pamg_mat_value_bits(const pamg_mat* A, int* bits) {
+    if (!A || !bits) return fail(PAMG_E_ARG, "mat_value_bits: bad args");
+    *bits = A->value_bits;
+    return PAMG_OK;
 }
 
 // Locality permutation inside the device layout: device row i = caller row row_perm[i], own

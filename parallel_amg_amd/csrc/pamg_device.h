@@ -379,6 +379,10 @@ struct RpatSet {
 // column at d_bcol[(d_soff[s] + k) * kEllW + l] (-1: padding), the row's bs entries of that block at
 // d_val[((d_soff[s] + k) * kEllW + l) * bs + e] — bs adjacent doubles per lane, contiguous over the wave.
 // 8 + 4 / bs bytes per stored nonzero, bs times the lanes of the node-per-lane form.
+//
+// Through pamg_mat_upload_f32 (SPEC §S15) either form holds its values as binary32 in d_val32, the same slots
+// in the same order (d_val stays null): 4 + 4 / bs^2 and 4 + 4 / bs bytes per stored nonzero. The kernels widen
+// each value exactly before the fp64 product.
 constexpr int kBsrSlices = kBlock / kEllW;  // slices (waves) per workgroup
 struct BsrSet {
     int bs = 0;
@@ -387,6 +391,7 @@ struct BsrSet {
     int64_t* d_soff = nullptr;    // nslices + 1
     int* d_bcol = nullptr;        // slots
     double* d_val = nullptr;      // slots * bs * bs
+    float* d_val32 = nullptr;     // SPEC §S15 (pamg_mat_upload_f32): the same slots as binary32, d_val null
     int grid = 0;                 // workgroups of k_rows_bsr
     bool row_lanes = false;       // the row-per-lane form: nslices, slots and the arrays are per scalar row
 };
@@ -507,6 +512,7 @@ struct pamg_mat {
     // point blocks (SPEC §S12; pamg_mat_set_block_diag): bs = 1 none; else row i's bs entries of its node
     // block D_m at d_bdiag[i * bs ..] and of D_m^-1 at d_binv[i * bs ..], beside d_diag
     bool permuted = false;  // uploaded through pamg_mat_upload_perm with a row or column permutation
+    int value_bits = 64;    // 32: uploaded through pamg_mat_upload_f32 (SPEC §S15; the values are RN32's)
     int bs = 1;
     double* d_bdiag = nullptr;
     double* d_binv = nullptr;

@@ -606,6 +606,8 @@ struct pamg_hier {
     pamg_ctx* ctx = nullptr;
     int L = 0;
     std::vector<const pamg_mat*> A, P, R;
+    // the operator PCG forms b - A x and A p with (pamg_hier_set_outer; SPEC §S15), or null: A[0]
+    const pamg_mat* outer = nullptr;
     std::vector<double> omega;
     // per-level work vectors (level 0: t, r only; x and b belong to the caller)
     std::vector<double*> x, b, t, r;
@@ -1946,6 +1948,7 @@ int pamg_hier_set_perm(pamg_hier* H, int64_t n, const int64_t* perm) {
     dfree(H->pb);
     if (!perm || n == 0) return PAMG_OK;
     if (ctx->nranks > 1) return fail(PAMG_E_STATE, "hier_set_perm: one part only (permute a partition's rows before setup)");
+    if (H->outer) return fail(PAMG_E_STATE, "hier_set_perm: the hierarchy has an outer operator (pamg_hier_set_outer)");
     const pamg_mat* A0 = H->A[0];
     if (n != H->nown[0] || n != A0->ncols)
         return fail(PAMG_E_ARG, "hier_set_perm: %lld entries for a %lld-row level 0", (long long)n, (long long)H->nown[0]);
@@ -1962,6 +1965,26 @@ int pamg_hier_set_perm(pamg_hier* H, int64_t n, const int64_t* perm) {
     HIPC(hipMemcpy(H->d_perm, p.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     CHECK(dzero(H->ctx, H->px, sizeof(double) * (n + kVecPad)));
     CHECK(dzero(H->ctx, H->pb, sizeof(double) * (n + kVecPad)));
+    return PAMG_OK;
+}
+
+// SPEC §S15: the operator pamg_pcg, pamg_pcg_resident and pamg_pcg_multi use for b - A x and A p (the exact
+// A beside a hierarchy of rounded operators); NULL: A[0] again. The V-cycle is untouched.
+int pamg_hier_set_outer(pamg_hier* H, const pamg_mat* A) {
+    if (!H) return fail(PAMG_E_ARG, "hier_set_outer: NULL");
+    if (A) {
+        const pamg_mat* A0 = H->A[0];
+        if (H->d_perm) return fail(PAMG_E_STATE, "hier_set_outer: the hierarchy has a level-0 permutation");
+        if (A->ctx != H->ctx || A->permuted) return fail(PAMG_E_ARG, "hier_set_outer: an operator of another context or numbering");
+        if (A->nrows != A0->nrows || A->ncols != A0->ncols)
+            return fail(PAMG_E_ARG, "hier_set_outer: a %lld x %lld operator for a %lld x %lld level 0", (long long)A->nrows,
+                        (long long)A->ncols, (long long)A0->nrows, (long long)A0->ncols);
+        if (A->plan != A0->plan) return fail(PAMG_E_ARG, "hier_set_outer: the operator has another column plan than level 0");
+    }
+    CHECK(set_device(H->ctx));
+    HIPC(hipStreamSynchronize(H->ctx->s_comp));
+    drop_pcg_graphs(H);  // (they hold the q = A p launch)
+    H->outer = A;
     return PAMG_OK;
 }
 
@@ -2213,7 +2236,7 @@ int pamg_pcg(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* b, double
              int maxit, int* iters, double* res_hist) {
     if (!ctx || !H || !x || !b || maxit < 0 || !(rtol >= 0.0) || H->ctx != ctx)
         return fail(PAMG_E_ARG, "pcg: bad args");
-    const pamg_mat* A = H->A[0];
+    const pamg_mat* A = H->outer ? H->outer : H->A[0];
     CHECK(check_vec_for(A, x, "pcg"));
     if (b->n_own != A->nrows) return fail(PAMG_E_ARG, "pcg: b size mismatch");
     CHECK(set_device(ctx));
@@ -2310,7 +2333,7 @@ int pcg_half_enqueue(pamg_hier* H, double* xd, int half) {
     const int np = pamg::dot_partials(n);
     double *r = H->pcg_r, *z = H->pcg_z, *p = H->pcg_p, *q = H->pcg_q;
     if (half == 0) {
-        CHECK(apply(ctx, H->A[0], pamg::OP_SPMV, p, nullptr, q, 0.0));
+        CHECK(apply(ctx, H->outer ? H->outer : H->A[0], pamg::OP_SPMV, p, nullptr, q, 0.0));
         pamg::launch_pcg_half_a(n, H->pcg_S, p, q, xd, r, ctx->d_red, np, H->pcg_hist, s);
         HIPC(hipMemcpyAsync(H->pcg_slot, &H->pcg_S->k, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     } else {
@@ -2350,7 +2373,7 @@ int pamg_pcg_resident(pamg_ctx* ctx, pamg_hier* H, pamg_vec* x, const pamg_vec* 
         return fail(PAMG_E_ARG, "pcg_resident: bad args");
     if (ctx->nranks > 1)
         return fail(PAMG_E_STATE, "pcg_resident: one part only (the scalars are not summed across ranks; use pamg_pcg)");
-    const pamg_mat* A = H->A[0];
+    const pamg_mat* A = H->outer ? H->outer : H->A[0];
     CHECK(check_vec_for(A, x, "pcg_resident"));
     if (b->n_own != A->nrows) return fail(PAMG_E_ARG, "pcg_resident: b size mismatch");
     CHECK(set_device(ctx));
@@ -3054,7 +3077,7 @@ int pamg_pcg_multi(pamg_ctx* ctx, pamg_hier* H, pamg_vec* X, const pamg_vec* B, 
         return fail(PAMG_E_ARG, "pcg_multi: bad args");
     CHECK(check_multi_hier(ctx, H, X, B, "pcg_multi"));
     CHECK(set_device(ctx));
-    const pamg_mat* A = H->A[0];
+    const pamg_mat* A = H->outer ? H->outer : H->A[0];
     const int k = X->ncols;
     const int64_t n = A->nrows;
     CHECK(ensure_multi(H, k));

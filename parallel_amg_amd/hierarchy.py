@@ -8,7 +8,7 @@ global matrices and evaluated in the same order (§S4.5).
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -467,3 +467,30 @@ def spmv_host(A: HCSR, x_full: np.ndarray) -> np.ndarray:
             s = s + A.val[k] * x_full[A.col[k]]
         y[i] = s
     return y
+
+
+def round_f32(M: HCSR) -> HCSR:
+    """M with every value rounded to binary32 and widened again (SPEC §S15: round to nearest even,
+    subnormals and signed zeros kept, non-finite values as they are); ValueError where a finite value
+    rounds to an infinity."""
+    if M is None:
+        return None
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.asarray(M.val, np.float64).astype(np.float32).astype(np.float64)
+    bad = np.flatnonzero(np.isinf(v) & np.isfinite(M.val))
+    if len(bad):
+        k = int(bad[0])
+        i = int(np.searchsorted(M.rowptr, k, side="right")) - 1
+        raise ValueError(f"round_f32: the value {float(M.val[k])!r} of row {i}, column {int(M.col[k])} "
+                         "rounds to an infinite binary32")
+    return HCSR.from_arrays(M.rowptr, M.col, v, M.ncols)
+
+
+def round_values(H: HostHierarchy) -> HostHierarchy:
+    """A copy of H whose A_l, P_l and R_l hold values rounded to binary32 (SPEC §S15), each rounded
+    on its own: what ``AMGSolver(..., values="f32")`` runs its V-cycle on, as fp64 matrices. The
+    weights, the bounds rho_l, the coarsest inverse, the plans and the aggregates are H's own objects.
+    ValueError where a value overflows binary32."""
+    levels = [{p: replace(lp, A=round_f32(lp.A), P=round_f32(lp.P), R=round_f32(lp.R)) for p, lp in lev.items()}
+              for lev in H.levels]
+    return replace(H, levels=levels)

@@ -405,7 +405,7 @@ class PSparseMatrix:
 
     def __init__(self, ctx: Context, M: HCSR, plan: HostPlan | None = None,
                  dplan: DevicePlan | None = None, row_perm=None, col_perm=None, tag: int = 0,
-                 block_size: int = 1, block_rows: int = 1):
+                 block_size: int = 1, block_rows: int = 1, value_bits: int = 64):
         """``row_perm`` / ``col_perm`` (pamg_mat_upload_perm): device row i is row
         ``row_perm[i]`` of M, device own column k is own column ``col_perm[k]`` (None: the
         identity); rows keep their storage order, so row sums keep their bits. ``tag``: the
@@ -416,8 +416,15 @@ class PSparseMatrix:
         permutation: renumber the nodes before setup. ``block_rows`` > 1
         (pamg_mat_upload_block_rows): the same for an operator that may be rectangular, between two
         node-major spaces of that block size (the P and R of a nodal hierarchy, SPEC §S14); no diagonal is
-        asked for and ``self.blocked`` tells whether the block-row layout was taken."""
+        asked for and ``self.blocked`` tells whether the block-row layout was taken. ``value_bits=32``
+        (pamg_mat_upload_f32, SPEC §S15; not with a permutation): the values are rounded to binary32 and
+        the operator is the rounded one in every respect; in the block-row layout they are stored as 4-byte
+        floats (``self.f32_storage``), elsewhere as fp64. A value that overflows binary32 is a PamgError."""
         block_size, block_rows = int(block_size), int(block_rows)
+        if value_bits not in (32, 64):
+            raise ValueError("PSparseMatrix: value_bits is 32 or 64")
+        if value_bits == 32 and (row_perm is not None or col_perm is not None):
+            raise ValueError("PSparseMatrix: value_bits=32 cannot be combined with row_perm / col_perm")
         if block_size != 1 and block_rows != 1:
             raise ValueError("PSparseMatrix: give block_size (square operators) or block_rows, not both")
         if (block_size > 1 or block_rows > 1) and (row_perm is not None or col_perm is not None):
@@ -434,7 +441,11 @@ class PSparseMatrix:
             col, ncols = M.col, M.ncols
         col = np.ascontiguousarray(col, np.int32)
         h = C.c_void_p()
-        if block_size != 1:
+        if value_bits == 32:
+            call("pamg_mat_upload_f32", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
+                 ptr(M.val), 0, dplan.handle if dplan is not None else None, max(block_size, block_rows),
+                 int(block_rows != 1), C.byref(h))
+        elif block_size != 1:
             call("pamg_mat_upload_blocked", ctx.handle, M.nrows, ncols, ptr(M.rowptr), ptr(col), 0,
                  ptr(M.val), 0, dplan.handle if dplan is not None else None, block_size, C.byref(h))
         elif block_rows != 1:
@@ -460,11 +471,14 @@ class PSparseMatrix:
         self.block_size = 1
         self.blocked = False  # the rows run in the block-row layout (pamg_mat_layout bit 15)
         self.row_lanes = False
+        self.value_bits = int(value_bits)
+        self.f32_storage = False  # the block-row layout holds 4-byte values (pamg_mat_layout bit 16)
         if block_size != 1 or block_rows != 1:
             lay = (C.c_int * 10)()
             call("pamg_mat_layout", h, 0, lay)
             self.blocked = bool(lay[9] & 32768)
             self.row_lanes = self.blocked and lay[6] == 1  # its row-per-lane form (k_rows_bsr_r)
+            self.f32_storage = bool(lay[9] & 65536)
 
     def set_block_diag(self, bs: int = 1, blocks=None, inv=None):
         """Attach the point blocks of the own rows and their inverses (``hcsr.block_diag``'s arrays;

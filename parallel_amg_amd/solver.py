@@ -49,7 +49,7 @@ class _LevelOps:
 
 class AMGSolver:
     def __init__(self, ctx: Context, H: HostHierarchy, part: int = 0, graph: bool | None = None,
-                 reorder: str = "auto", block_layout=None):
+                 reorder: str = "auto", block_layout=None, values: str = "f64"):
         """``block_layout``: None, a block size (level 0) or a ``{level: block size}`` dict — those
         levels' operators are uploaded through pamg_mat_upload_blocked and, where they qualify (every
         node's rows store the same whole blocks, one part without ghost columns), run in the
@@ -78,7 +78,34 @@ class AMGSolver:
         renumberings and the levels aggregated from them), "on" on every level, "off" never.
         A_l, P_l and R_l are uploaded through the fine and coarse permutations with each row
         in its storage order, and the V-cycle gathers / scatters the caller's level-0 vectors
-        (pamg_hier_set_perm), so every result keeps the unpermuted hierarchy's bits."""
+        (pamg_hier_set_perm), so every result keeps the unpermuted hierarchy's bits.
+
+        ``values="f32"`` (SPEC §S15; the default "f64" is the path above, untouched): the V-cycle runs on
+        ``hierarchy.round_values(H)`` — every A_l, P_l and R_l rounded to binary32, uploaded with
+        ``value_bits=32``, so the levels in the block-row layout (``block_layout``) stream 4-byte values — while
+        ``pcg`` and ``pcg_multi`` solve with the exact A_0: it is uploaded once more in fp64 (in the block-row
+        layout where level 0 has it) and set as the outer operator (``set_fine_operator``). ``fine_operator()``
+        and ``A[0]`` return the exact operator, ``A_dev[0]`` the rounded one; ``set_block_size`` and
+        ``estimate_lmax`` read the rounded matrices, the weights and bounds stay the fp64 setup's. A stationary
+        ``vcycle`` iterates on the rounded A_0. Cost in memory: level 0 is held 1.5 times (the fp64 copy beside
+        the 4-byte one). Level 0 must stay unpermuted (ValueError: ``reorder="off"``); a permuted coarser level
+        goes through the permuted fp64 upload with its values already rounded: it is the rounded operator, stored
+        in fp64, and its ``value_bits`` reads 64 (the mark is the f32 upload's; the permuted upload has none). ValueError where a value overflows binary32. Which to take
+        ("Single-precision values"; one MI355X, 80^3 nodes of three unknowns with variable
+        coefficients, PCG to 1e-8 with block Jacobi V(1,1), ``lmax="estimate"``): take it together with
+        ``block_layout`` when PCG is the solver — 6.29 ms against 7.22 in grid order and 9.96 against 11.16 with the
+        nodes renumbered at random, 7 and 8 iterations either way, the same final residual; a level-0 pass takes
+        0.61 and 0.76 of its fp64 time. Without ``block_layout`` nothing stores 4-byte values and nothing gets
+        faster. On the nodal hierarchy it gains the same 13 % (20.5 ms against 23.5) and does not mend that
+        hierarchy's loss against the scalar one."""
+        if values not in ("f64", "f32"):
+            raise ValueError(f"values: {values!r} ('f64' or 'f32')")
+        self.values = values
+        H_exact = H
+        if values == "f32":
+            from .hierarchy import round_values
+            H = round_values(H)
+        vbits = 32 if values == "f32" else 64
         self.ctx, self.part, self.L = ctx, part, H.nlevels
         # the level operators as the hierarchy holds them (device numbering where permuted);
         # ``A`` (below) gives level 0 in the caller's numbering
@@ -114,6 +141,9 @@ class AMGSolver:
                 order, before, after = locality_order(H.levels[l][part].A, mode)
                 self.perm[l] = order
                 self.span[l] = (round(before, 1), round(after, 1))
+        if values == "f32" and self.perm[0] is not None:
+            raise ValueError("values='f32': level 0 is uploaded with a locality permutation, which the outer "
+                             "operator does not take (build the solver with reorder='off')")
         transfers = {"P": {}, "R": {}}
         if isinstance(block_layout, str):
             if block_layout != "all":
@@ -151,15 +181,19 @@ class AMGSolver:
             pl = self.perm[l]
             pn = self.perm[l + 1] if l + 1 < H.nlevels else None
             # plan tags (pamg_plan_set_tag): level and operator, the same on every part
+            # (a permuted level of a values="f32" hierarchy: its rounded values through the fp64 upload)
             self.A_dev.append(PSparseMatrix(ctx, lp.A, lp.planA, row_perm=pl, col_perm=pl, tag=plan_tag(l, "A"),
-                                            block_size=self.block_layout.get(l, 1)))
+                                            block_size=self.block_layout.get(l, 1),
+                                            value_bits=64 if pl is not None else vbits))
             self.omega.append(lp.omega)
             if l < H.nlevels - 1:
                 self.P.append(PSparseMatrix(ctx, lp.P, None if l + 1 >= rep else lp.planP,
                                             row_perm=pl, col_perm=pn, tag=plan_tag(l, "P"),
-                                            block_rows=self.block_layout_P.get(l, 1)))
+                                            block_rows=self.block_layout_P.get(l, 1),
+                                            value_bits=64 if pl is not None or pn is not None else vbits))
                 self.R.append(PSparseMatrix(ctx, lp.R, lp.planR, row_perm=pn, col_perm=pl, tag=plan_tag(l, "R"),
-                                            block_rows=self.block_layout_R.get(l, 1)))
+                                            block_rows=self.block_layout_R.get(l, 1),
+                                            value_bits=64 if pl is not None or pn is not None else vbits))
         self.level_rows = [int(H.levels[l][part].A.nrows) for l in range(H.nlevels)]
         self.n_coarse = H.n_coarse
         L = self.L
@@ -183,6 +217,20 @@ class AMGSolver:
             call("pamg_hier_set_perm", h, len(p0), ptr(p0))
         if graph is not None:
             self.set_graph(graph)
+        self._outer = None
+        if values == "f32":
+            lp = H_exact.levels[0][part]
+            self.set_fine_operator(PSparseMatrix(ctx, lp.A, lp.planA, dplan=self.A_dev[0].plan,
+                                                 block_size=self.block_layout.get(0, 1)))
+
+    def set_fine_operator(self, A: PSparseMatrix | None):
+        """The operator ``pcg`` and ``pcg_multi`` form b - A x and A p with (pamg_hier_set_outer, SPEC §S15),
+        and ``fine_operator()`` / ``A[0]`` return: the exact fp64 A_0 around a hierarchy of rounded operators.
+        ``None`` restores the hierarchy's own level 0. A has level 0's shape and shares its column plan
+        (``PSparseMatrix(..., dplan=solver.A_dev[0].plan)``); PamgError otherwise, and on a hierarchy whose
+        level 0 is permuted. The V-cycle, and a stationary ``vcycle``'s residual history, stay level 0's own."""
+        call("pamg_hier_set_outer", self._h, A.handle if A is not None else None)
+        self._outer = A
 
     @property
     def A(self) -> "_LevelOps":
@@ -202,6 +250,8 @@ class AMGSolver:
         """The level-0 operator in the caller's numbering (for b = A x and residuals of the
         caller's vectors): the hierarchy's own A_0 when level 0 is not permuted, else an
         unpermuted upload (made once, kept)."""
+        if self._outer is not None:
+            return self._outer
         if self.perm[0] is None:
             return self.A_dev[0]
         if self._A0_caller is None:

@@ -47,7 +47,11 @@ def demangle(names):
 
 
 def short(name):
-    return re.sub(r"^(void )?pamg::\(anonymous namespace\)::", "", name).split("(")[0]
+    """The kernel's name and template arguments. The block-row kernels' trailing value-type argument
+    ``double`` is the default of a parameter added after the integers (VT): such an instantiation is the
+    kernel an older build names without it."""
+    s = re.sub(r"^(void )?pamg::\(anonymous namespace\)::", "", name).split("(")[0]
+    return re.sub(r"^(k_rows_bsr(?:_mc|_r)?<.*), double>$", r"\1>", s)
 
 
 def by_template(log):
